@@ -18,14 +18,19 @@ rest.  Every rung starts from NaN-poisoned halo rows, verifies its first sweep a
 values in the exchanged fields and re-poisoned halos (an exchange that delivers once does not pass).  --stepper torch /
 --backend gloo are the in-process bring-up modes.
 
+N = 1 without --full is the plain line: set-up, W warm-up sweeps, the K timed sweeps, --dump-outputs DIR if given (the output
+arrays after the last timed sweep, dump_outputs), the JSON line.  --full adds the checks and side measurements below that take
+time or runs of their own: the oracle check of the first warm-up sweep (verified_vs_oracle; fp32: fp32_vs_fp64_oracle), the box
+probe (roofline.box_*, gpu_state), wrf_rows, the same-run HBM traffic and cpu_baseline.
+
 Output keys beyond the driver's contract:
   roofline      algorithmic HBM bytes of one sweep (W*NI*NJ*(11*NK+14))
                 divided by the HIP-event time of the kernel launches, against 8 TB/s per GPU
-  cpu_baseline  the fastest CPU path -- the build's Fortran-90 restatement or the C port, both j-tiled over the
+  cpu_baseline  (--full) the fastest CPU path -- the build's Fortran-90 restatement or the C port, both j-tiled over the
                 host cores -- timed on the WHOLE domain where host memory and the leg's budget allow, else on a bounded
                 j-slab sample of it (rank 0, N=1; the record says which)
   config.idim ... aligned, wrf_rows   (N = 1) the memory layout of the timed state (rows padded to whole 128-byte lines), and the same
-                sweeps + PMC passes on WRF's own unpadded extents ims:ime = 0:NI+1 in the same run
+                sweeps + PMC passes on WRF's own unpadded extents ims:ime = 0:NI+1 in the same run (--full)
   transports, ladder, preflight   (N > 1) every rung's outcome; per-rank roofline figures against 8 TB/s x N
   placement     the bench state is allocated by amt_domain_create (the product call a Fortran / C host makes once), whose
                 default placement sampling keeps the fastest of 4 allocations of the state: `value` is therefore what a
@@ -126,6 +131,16 @@ def parse():
     ap.add_argument("--comm-timeout", type=float, default=120.0,
                     help="N > 1: most seconds a rank waits in the communicator set-up (ncclCommInitRank) and in the "
                          "first halo exchange before it ends itself with a diagnosis")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: also verify the first sweep against the oracle (fp32: and its error against fp64), probe the "
+                         "box (streaming ceilings, clock ramp, clocks and power), time WRF's unpadded rows, re-measure the HBM "
+                         "traffic with rocprofv3 child passes and run the CPU baseline; the --no-* options above then still "
+                         "switch single legs off.  Without it a single-GPU run sets up, warms up, times --steps sweeps and "
+                         "prints the line.  (N > 1 runs always verify.)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="N = 1: after the timed sweeps write the routine's output arrays as DIR/<name>.npy in the run's "
+                         "precision, over the domain's own extents; an array of more than 2^20 elements is sampled at fixed "
+                         "indices drawn from --seed (dump_outputs)")
     return ap.parse_args()
 
 
@@ -753,6 +768,11 @@ def run_rank(a):
         raise SystemExit(0)
     if a.traffic_layouts:
         return traffic_child(a)
+    if world == 1 and not a.full:
+        # the plain single-GPU line: only what its headline figure needs (set-up, warm-up, timed sweeps); the checks and the
+        # side measurements are --full's
+        a.no_verify = a.no_box_probe = a.no_traffic = a.no_cpu_baseline = True
+        a.wrf_rows_steps = 0
     prebuild = start_cpu_prebuild() if world == 1 and not a.no_cpu_baseline else None
     smi_idle = gpu_state_smi() if rank == 0 and not a.no_box_probe else None     # before anything touches the GPU
     import torch
@@ -887,6 +907,8 @@ def run_rank(a):
     wall = time.perf_counter() - t0
     ev_ms = ev0.elapsed_time(ev1)
     per_sweep = [(ev0 if k == 0 else marks[k - 1]).elapsed_time(marks[k]) for k in range(a.steps)]
+    if a.dump_outputs:
+        dump_outputs(pkg, dev, a.dump_outputs, a.seed)
 
     rank_ms = [ev_ms / max(a.steps, 1)] * 2                       # min, max over ranks of the event ms per sweep
     if world > 1:
@@ -1099,6 +1121,30 @@ def time_wrf_rows(a, pkg, device, dtype, abytes):
             "steps": a.wrf_rows_steps, "ms_per_step": round(ms, 4), "ms_per_step_median": round(float(np.median(per)), 4),
             "frac": round(abytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "achieved_GBps": round(abytes / (ms * 1e-3) / 1e9, 1),
             "placement_probe_ms": probe, "kernel": kernel}
+
+
+DUMP_SAMPLE = 1 << 20        # elements per output at most: 7 outputs x 8 MiB in fp64 stay under 64 MB
+
+
+def dump_outputs(pkg, dev, out_dir, seed):
+    """--dump-outputs: what the timed sweeps left in the routine's output arrays (synth.OUTPUTS), one DIR/<name>.npy each in
+    the run's precision.  Every array is cut to the domain's own extents (i = 0:NI+1, k = 1:NK+1, j = 0:NJ+1), so the padding
+    of the timed layout never shows; one of more than DUMP_SAMPLE elements becomes a 1-D sample at sorted flat indices of
+    that cut, drawn by a generator seeded with --seed: the same elements in every run with the same arguments."""
+    import torch
+    b = dev.bounds
+    gni, gnk, gnj = dev.global_dims
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    for name in pkg.synth.OUTPUTS:
+        t = dev.arrays[name]
+        js, is_ = slice(0 - b.jms, gnj + 2 - b.jms), slice(0 - b.ims, gni + 2 - b.ims)
+        t = t[js, 1 - b.kms: gnk + 2 - b.kms, is_] if t.dim() == 3 else t[js, is_]
+        if t.numel() > DUMP_SAMPLE:
+            flat = np.sort(rng.choice(t.numel(), size=DUMP_SAMPLE, replace=False))
+            t = t[tuple(torch.from_numpy(c).to(t.device) for c in np.unravel_index(flat, tuple(t.shape)))]
+        np.save(out / f"{name}.npy", t.contiguous().cpu().numpy())
 
 
 # =====================================================================================================================
@@ -1681,6 +1727,8 @@ def supervisor_line(a, world, pre, results, ladder, good):
 
 def main():
     a = parse()
+    if a.dump_outputs and (a.gpus > 1 or a.emulate_world > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        raise SystemExit("bench.py --dump-outputs serves the single-GPU line only (--gpus 1)")
     if a.rung_child:
         return rung_child(a)
     if a.emulate_world > 1:

@@ -55,7 +55,7 @@ def build(ref: bool | None = None, extras: bool = False) -> None:
     if extras:
         subprocess.run(["make", "-C", str(HERE), "extras"], check=True, capture_output=True)
     if ref is None:
-        ref = Path("/root/reference/module_small_step_em.f90").exists()
+        ref = subprocess.run(["make", "-s", "-C", str(HERE), "have-ref"], capture_output=True).returncode == 0
     if ref:
         subprocess.run(["make", "-C", str(HERE), "ref"], check=True, capture_output=True)
 

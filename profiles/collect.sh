@@ -16,12 +16,12 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 export AMT_MARCH_VERBOSE=1     # the launcher's plan (kernel, waves, LDS, grid) goes into the logs
 R="rocprofv3 --output-format csv"
-$R --kernel-trace --stats -d $OUT/trace -o trace -- python3 bench.py $ARGS > $OUT/bench_trace.log 2>&1
-$R --kernel-trace --pmc FETCH_SIZE -d $OUT/fetch -o fetch -- python3 bench.py $ARGS > $OUT/bench_fetch.log 2>&1
-$R --kernel-trace --pmc WRITE_SIZE -d $OUT/write -o write -- python3 bench.py $ARGS > $OUT/bench_write.log 2>&1
-$R --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum -d $OUT/l2 -o l2 -- python3 bench.py $ARGS > $OUT/bench_l2.log 2>&1
+$R --kernel-trace --stats -d $OUT/trace -o trace -- python3 bench.py --full $ARGS > $OUT/bench_trace.log 2>&1
+$R --kernel-trace --pmc FETCH_SIZE -d $OUT/fetch -o fetch -- python3 bench.py --full $ARGS > $OUT/bench_fetch.log 2>&1
+$R --kernel-trace --pmc WRITE_SIZE -d $OUT/write -o write -- python3 bench.py --full $ARGS > $OUT/bench_write.log 2>&1
+$R --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum -d $OUT/l2 -o l2 -- python3 bench.py --full $ARGS > $OUT/bench_l2.log 2>&1
 $R --kernel-trace --pmc FETCH_SIZE -d $OUT/calib_fetch -o calib -- python3 profiles/calib.py > $OUT/calib_fetch.log 2>&1
 $R --kernel-trace --pmc WRITE_SIZE -d $OUT/calib_write -o calib -- python3 profiles/calib.py > $OUT/calib_write.log 2>&1
-python3 bench.py $ARGS > $OUT/bench_plain.log 2>&1
+python3 bench.py --full $ARGS > $OUT/bench_plain.log 2>&1
 find $OUT -name "*.csv" | head -50
 python3 profiles/summarize.py $TAG $OUT

@@ -9,7 +9,7 @@ G2="SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_INSTS_VALU SQ_INST_LEVEL_V
 run() {  # tag counters args...
   local tag=$1 cnt=$2; shift 2
   local t0=$(date +%s)
-  timeout 600 rocprofv3 --output-format csv --kernel-trace --kernel-include-regex amt_march --pmc $cnt -d $O/$tag -o pmc -- python3 bench.py "$@" $B > $O/$tag.log 2>&1
+  timeout 600 rocprofv3 --output-format csv --kernel-trace --kernel-include-regex amt_march --pmc $cnt -d $O/$tag -o pmc -- python3 bench.py --full "$@" $B > $O/$tag.log 2>&1
   echo "$tag rc $? $(( $(date +%s) - t0 )) s" >> $O/times.txt
   python3 - "$O/$tag" <<'PY' > $O/$tag.txt
 import csv, glob, sys, collections

@@ -15,6 +15,6 @@ timeout 1500 python3 -m pytest tests/test_gpu_13_fullsize.py tests/test_gpu_90_b
 bash profiles/collect.sh r03_f64_4096x60x4096 --steps 5 --warmup 1 --no-cpu-baseline --no-verify --no-box-probe --probe-placements 1 > $O/collect_f64.log 2>&1
 bash profiles/collect_slab.sh > $O/collect_slab.log 2>&1
 mkdir -p gpurun_out/profiles_r03; cp profiles/r03_*kernel_stats.csv profiles/r03_*pmc.json profiles/hbm_traffic.json gpurun_out/profiles_r03/ 2>/dev/null
-rocprofv3 --output-format json --kernel-trace --pmc TCC_EA0_RDREQ -d $O/chan_json -o chan -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-verify --no-box-probe --probe-placements 1 > $O/chan_json.log 2>&1
+rocprofv3 --output-format json --kernel-trace --pmc TCC_EA0_RDREQ -d $O/chan_json -o chan -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-verify --no-box-probe --probe-placements 1 > $O/chan_json.log 2>&1
 ls -la $O/chan_json/*/ 2>/dev/null | head; 
 tail -6 $O/price_*.txt $O/unaligned_*.txt | cut -c1-160; tail -3 $O/pytest.log; tail -5 $O/collect_slab.log

@@ -9,9 +9,9 @@ rm -rf oracle/_native
 ( time timeout 3300 python3 -m pytest tests -x -q -m gpu ) > $O/pytest.log 2>&1; echo "pytest rc $?" >> $O/pytest.log
 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc $?" >> $O/smoke.log
 rm -rf oracle/_native
-( time python3 bench.py ) > $O/bench_noargs.json 2> $O/bench_noargs.err
-( time python3 bench.py --gpus 1 --steps 20 --warmup 5 ) > $O/bench_driver.json 2> $O/bench_driver.err
-rocprofv3 --output-format csv --kernel-trace --stats -d $O/trace -o trace -- python3 bench.py --gpus 1 --steps 20 --warmup 3 --no-cpu-baseline --no-traffic > $O/bench_traced.json 2> $O/bench_traced.err
+( time python3 bench.py --full ) > $O/bench_noargs.json 2> $O/bench_noargs.err
+( time python3 bench.py --full --gpus 1 --steps 20 --warmup 5 ) > $O/bench_driver.json 2> $O/bench_driver.err
+rocprofv3 --output-format csv --kernel-trace --stats -d $O/trace -o trace -- python3 bench.py --full --gpus 1 --steps 20 --warmup 3 --no-cpu-baseline --no-traffic > $O/bench_traced.json 2> $O/bench_traced.err
 for f in $(find $O/trace -name "*kernel_stats.csv"); do cp $f $O/kernel_stats.csv; done; rm -rf $O/trace
 ( time python3 bench.py --gpus 2 --share-gpu --steps 10 --warmup 3 --no-box-probe ) > $O/bench_share2_both.json 2> $O/bench_share2_both.err
 tail -n 3 $O/pytest.log; tail -n 2 $O/smoke.log; grep real $O/bench_noargs.err $O/bench_driver.err $O/bench_share2_both.err; head -4 $O/kernel_stats.csv | cut -c1-200

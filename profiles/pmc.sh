@@ -5,7 +5,7 @@ TAG=$1; CNT=$2; shift 2
 ARGS=${@:---steps 3 --warmup 1 --no-cpu-baseline --no-verify}
 OUT=gpurun_out/pmc_$TAG
 mkdir -p $OUT; export TMPDIR=/tmp
-rocprofv3 --output-format csv --kernel-trace --pmc $CNT -d $OUT -o pmc -- python3 bench.py $ARGS > $OUT/bench.log 2>&1
+rocprofv3 --output-format csv --kernel-trace --pmc $CNT -d $OUT -o pmc -- python3 bench.py --full $ARGS > $OUT/bench.log 2>&1
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, collections
 acc = collections.defaultdict(lambda: collections.defaultdict(list))

@@ -4,7 +4,7 @@ O=gpurun_out/fetch80; mkdir -p $O
 A="--nk 80 --nj 2048 --steps 4 --warmup 1 --no-cpu-baseline --no-verify --no-traffic --no-box-probe --probe-placements 1"
 for r in 64 128 32; do
   export AMT_MARCH_JROWS=$r
-  rocprofv3 --output-format csv --kernel-trace --pmc FETCH_SIZE -d $O/f$r -o f -- python3 bench.py $A > $O/bench_$r.log 2>&1
+  rocprofv3 --output-format csv --kernel-trace --pmc FETCH_SIZE -d $O/f$r -o f -- python3 bench.py --full $A > $O/bench_$r.log 2>&1
 done
 unset AMT_MARCH_JROWS
 python3 - <<'PY'

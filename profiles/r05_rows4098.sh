@@ -5,7 +5,7 @@ set -u
 export TMPDIR=/tmp
 O=gpurun_out/r05_rows4098; mkdir -p $O
 for JR in 0 512 256 128 64 32; do
-  AMT_MARCH_JROWS=$JR python3 bench.py --align-elems 1 --no-cpu-baseline --no-box-probe --steps 10 > $O/jrows$JR.json 2> $O/jrows$JR.err
+  AMT_MARCH_JROWS=$JR python3 bench.py --full --align-elems 1 --no-cpu-baseline --no-box-probe --steps 10 > $O/jrows$JR.json 2> $O/jrows$JR.err
 done
 python3 - $O <<'PY'
 import json, sys, glob

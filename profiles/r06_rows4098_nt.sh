@@ -12,7 +12,7 @@ for ROUND in 1 2; do
 for V in default nt0 nt2 nts1 nt0nts1; do
   for AL in 1 32; do
     if [ $V = default ]; then unset AMT_LIBRARY; else export AMT_LIBRARY=$PWD/$D/libamt_$V.so; fi
-    python3 bench.py --align-elems $AL --no-cpu-baseline --no-box-probe --steps 10 --warmup 3 > $O/${V}_al${AL}_r$ROUND.json 2> $O/${V}_al${AL}_r$ROUND.err
+    python3 bench.py --full --align-elems $AL --no-cpu-baseline --no-box-probe --steps 10 --warmup 3 > $O/${V}_al${AL}_r$ROUND.json 2> $O/${V}_al${AL}_r$ROUND.err
   done
 done
 done

@@ -4,7 +4,7 @@
 set -u
 export TMPDIR=/tmp
 O=gpurun_out/r06_rows4098_shapes; mkdir -p $O
-run() { tag=$1; shift; env "$@" python3 bench.py --align-elems 1 --no-cpu-baseline --no-box-probe --steps 10 --warmup 3 --wrf-rows-steps 0 > $O/$tag.json 2> $O/$tag.err; }
+run() { tag=$1; shift; env "$@" python3 bench.py --full --align-elems 1 --no-cpu-baseline --no-box-probe --steps 10 --warmup 3 --wrf-rows-steps 0 > $O/$tag.json 2> $O/$tag.err; }
 for R in 1 2; do
   run default_r$R AMT_X=1
   run xd1_r$R AMT_MARCH_XD=1

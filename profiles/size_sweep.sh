@@ -2,7 +2,7 @@
 # profiles/size_sweep.sh -- bench.py over a range of shapes (GPU box); one JSON line per shape
 # into gpurun_out/size_sweep.jsonl (summarised into profiles/r01_size_sweep.md by hand).
 OUT=gpurun_out/size_sweep.jsonl; : > $OUT
-run() { timeout 600 python bench.py --no-cpu-baseline --steps $1 --warmup 3 --dtype $2 --ni $3 --nk $4 --nj $5 2>/dev/null | tail -1 >> $OUT; }
+run() { timeout 600 python bench.py --full --no-cpu-baseline --steps $1 --warmup 3 --dtype $2 --ni $3 --nk $4 --nj $5 2>/dev/null | tail -1 >> $OUT; }
 run 500 f64 64 40 64
 run 500 f64 128 60 128
 run 300 f64 256 60 256

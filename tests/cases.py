@@ -1,6 +1,7 @@
 """Shared parity cases: shapes, flag combinations and tile calls (used by the golden
 generator, the CPU tests and the GPU tests)."""
 import hashlib
+from pathlib import Path
 
 import numpy as np
 
@@ -23,6 +24,20 @@ SHAPES = {
 }
 
 
+GOLDEN = Path(__file__).resolve().parent / "golden"
+# the reference's full output arrays (tests/golden/make_golden.py), in two files: one would pass 1 MiB
+GOLDEN_SMALL = {"golden_small.npz": ("16x8x16", "37x5x11_ragged"), "golden_small_shapes.npz": ("130x3x7_tile", "70x1x9_onelevel")}
+
+
+def load_small() -> dict:
+    """Every array of GOLDEN_SMALL's files, keyed '<shape>/<flags>/<dtype>/<output>'."""
+    out = {}
+    for name in GOLDEN_SMALL:
+        with np.load(GOLDEN / name) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
+
+
 def digest(a) -> str:
     return hashlib.sha256(np.ascontiguousarray(a).view(np.uint8).tobytes()).hexdigest()
 
@@ -34,3 +49,17 @@ def make_case(pkg, shape_name, flag_name, dtype, seed=12345, aligned=False):
         b = b.replace(**tile)
     return pkg.synth.make_patch(b, pkg.GridConfig(**FLAG_COMBOS[flag_name]), dtype=dtype, seed=seed,
                                 global_dims=(ni, nk, nj))
+
+
+EXTRA_TRIALS = 6          # extra seeds / shapes checked against the reference (tests/golden/extra_reference_digests.json)
+
+
+def extra_case(pkg, trial, dtype):
+    """Extra case `trial`: a random shape of 3..39 cells per axis (unpadded and padded rows in turn), a flag combination and a
+    seed of its own -- the same case on every host."""
+    rng = np.random.default_rng(0)
+    shapes = [tuple(int(x) for x in rng.integers(3, 40, 3)) for _ in range(EXTRA_TRIALS)]
+    ni, nk, nj = shapes[trial]
+    b = pkg.synth.domain_bounds(ni, nk, nj, aligned=bool(trial % 2))
+    flags = list(FLAG_COMBOS.values())[trial % 4]
+    return pkg.synth.make_patch(b, pkg.GridConfig(**flags), dtype=dtype, seed=1000 + trial)

@@ -8,9 +8,13 @@ It compiles the reference's module_configure.f90 + module_small_step_em.f90 from
 lie into oracle/_ref/ (oracle/Makefile `ref`; nothing is copied into the repository), runs
 `advance_mu_t` on this repository's seeded synthetic inputs and stores
 
-* golden_small.npz     -- all 7 outputs, full arrays, of 16x8x16 (every flag combination)
-                          and of the ragged / tile / one-level cases (flags none, specified)
+* golden_small.npz, golden_small_shapes.npz
+                       -- all 7 outputs, full arrays, of 16x8x16 (every flag combination)
+                          and of the ragged / tile / one-level cases (flags none, specified);
+                          split by shape (cases.GOLDEN_SMALL) so that no file passes 1 MiB
 * golden_digests.json  -- sha256 of every input and output array of every case (incl. 64x40x64)
+* extra_reference_digests.json -- sha256 of every array after the reference's call on the random
+                          extra cases of tests/cases.py (extra_case), fp32 and fp64
 
 The reference ships no golden vectors of its own (its drivers diff against an absent
 /data2/... directory), so these are the pinned known answers.
@@ -50,9 +54,25 @@ def main():
                 if shape == "16x8x16" or (shape in FULL_SHAPES and flag in ("none", "specified")):
                     for n in pkg.synth.OUTPUTS:
                         small[f"{key}/{n}"] = p.arrays[n]
-    np.savez_compressed(HERE / "golden_small.npz", **small)
+    for name, shapes in cases.GOLDEN_SMALL.items():
+        np.savez_compressed(HERE / name, **{k: v for k, v in small.items() if k.split("/")[0] in shapes})
     (HERE / "golden_digests.json").write_text(json.dumps(digests, indent=1, sort_keys=True))
     print(f"wrote {len(small)} arrays, {len(digests)} cases")
+    extra_reference_digests(pkg, oracle)
+
+
+def extra_reference_digests(pkg, oracle):
+    extra = {}
+    for dtype in (np.float32, np.float64):
+        recs = []
+        for trial in range(cases.EXTRA_TRIALS):
+            p = cases.extra_case(pkg, trial, dtype)
+            oracle.ref_advance_mu_t(*p.args())
+            recs.append({"bounds": list(p.bounds.as_tuple()),
+                         "fields": {n: cases.digest(p.arrays[n]) for n in pkg.synth.FIELD_NAMES}})
+        extra[np.dtype(dtype).name] = recs
+    (HERE / "extra_reference_digests.json").write_text(json.dumps(extra, indent=1, sort_keys=True))
+    print(f"wrote {sum(len(v) for v in extra.values())} extra cases")
 
 
 if __name__ == "__main__":

@@ -36,6 +36,46 @@ def test_bench_defaults_follow_the_driver_contract():
     assert a.steps > 0 and a.warmup >= 0
 
 
+def test_plain_run_is_the_default_and_full_is_an_option():
+    b = _bench()
+    sys_argv = sys.argv
+    try:
+        sys.argv = ["bench.py"]
+        a = b.parse()
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "out", "--steps", "7"]
+        f = b.parse()
+    finally:
+        sys.argv = sys_argv
+    assert a.full is False and a.dump_outputs == ""
+    assert f.full is True and f.dump_outputs == "out" and f.steps == 7
+
+
+def test_dump_outputs_cuts_the_domain_and_samples_large_arrays(pkg, monkeypatch, tmp_path):
+    """dump_outputs on CPU tensors of a padded patch: each output over the domain's own extents, whole while it is small, and a
+    sorted sample drawn from --seed beyond DUMP_SAMPLE elements -- the same elements every time."""
+    import numpy as np
+    import torch
+    b = _bench()
+    S = pkg.synth
+    ni, nk, nj = 21, 6, 9
+    host = S.make_patch(S.domain_bounds(ni, nk, nj, aligned=True, align_elems=8), pkg.GridConfig(), dtype=np.float32, seed=3,
+                        global_dims=(ni, nk, nj))
+    dev = S.Patch(host.bounds, host.config, {k: torch.from_numpy(v) for k, v in host.arrays.items()}, global_dims=(ni, nk, nj))
+    want = S.make_patch(S.domain_bounds(ni, nk, nj), pkg.GridConfig(), dtype=np.float32, seed=3)   # the same values, unpadded
+    b.dump_outputs(pkg, dev, tmp_path / "whole", 5)
+    for n in S.OUTPUTS:
+        got = np.load(tmp_path / "whole" / f"{n}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, want.arrays[n]), n
+    monkeypatch.setattr(b, "DUMP_SAMPLE", 100)
+    b.dump_outputs(pkg, dev, tmp_path / "s1", 5)
+    b.dump_outputs(pkg, dev, tmp_path / "s2", 5)
+    b.dump_outputs(pkg, dev, tmp_path / "s3", 6)
+    for n in ("ww", "t"):                                           # 3-D outputs: more than 100 elements
+        s1, s2, s3 = (np.load(tmp_path / d / f"{n}.npy") for d in ("s1", "s2", "s3"))
+        assert s1.shape == (100,) and np.array_equal(s1, s2) and not np.array_equal(s1, s3)
+        assert np.isin(s1, want.arrays[n]).all()
+
+
 def test_bench_refuses_to_run_without_a_gpu():
     import torch
     if torch.cuda.is_available():

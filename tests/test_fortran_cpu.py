@@ -26,8 +26,8 @@ def test_fortran_cpu_path_matches_reference_digests(pkg, oracle, key):
 
 
 def test_fortran_cpu_path_matches_reference_full_arrays(pkg, oracle):
-    small = np.load(GOLD / "golden_small.npz")
-    for key in sorted({k.rsplit("/", 1)[0] for k in small.files}):
+    small = cases.load_small()
+    for key in sorted({k.rsplit("/", 1)[0] for k in small}):
         shape, flag, dtname = key.split("/")
         p = cases.make_case(pkg, shape, flag, np.dtype(dtname))
         oracle.fortran_advance_mu_t(*p.args(), nthreads=3)

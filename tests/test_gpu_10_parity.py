@@ -281,9 +281,8 @@ def test_empty_and_degenerate_windows(pkg, oracle, torch_mod):
 
 def test_against_committed_golden_vectors(pkg, torch_mod):
     """HIP path straight against tests/golden (outputs of the reference Fortran itself)."""
-    from pathlib import Path
-    small = np.load(Path(__file__).resolve().parent / "golden" / "golden_small.npz")
-    keys = sorted({k.rsplit("/", 1)[0] for k in small.files})
+    small = cases.load_small()
+    keys = sorted({k.rsplit("/", 1)[0] for k in small})
     for key in keys:
         shape, flag, dtname = key.split("/")
         dev = cases.make_case(pkg, shape, flag, np.dtype(dtname)).to_device("cuda:0")

@@ -18,7 +18,6 @@ import cases
 from conftest import bits_equal
 
 ROOT = Path(__file__).resolve().parent.parent
-GOLD = ROOT / "tests" / "golden"
 pytestmark = pytest.mark.gpu
 
 
@@ -31,8 +30,8 @@ def _dropin(itemsize):
 
 
 def test_every_golden_case_through_the_reference_caller_and_config_type(pkg, oracle):
-    small = np.load(GOLD / "golden_small.npz")
-    keys = sorted({k.rsplit("/", 1)[0] for k in small.files})
+    small = cases.load_small()
+    keys = sorted({k.rsplit("/", 1)[0] for k in small})
     assert len(keys) >= 20
     pkg.load_library()                      # the product library first: the drop-in resolves amt_advance_mu_t_* from it
     done = 0

@@ -127,7 +127,7 @@ def test_torch_stepper_with_two_real_ranks():
 
 
 def test_single_gpu_line_carries_the_contract_keys():
-    out = _run(["--ni", "256", "--nj", "256", "--steps", "3", "--warmup", "2", "--cpu-seconds", "8", "--cpu-rows", "16"])
+    out = _run(["--full", "--ni", "256", "--nj", "256", "--steps", "3", "--warmup", "2", "--cpu-seconds", "8", "--cpu-rows", "16"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "verified_vs_oracle"):
         assert key in out, key
@@ -232,3 +232,30 @@ def test_more_ranks_than_devices_without_share_gpu_fails_in_the_preflight_not_af
     assert r.returncode != 0 and "only 1 GPU(s) visible" in r.stderr, r.stderr[-2000:]
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert time.time() - t0 < 120
+
+
+def test_plain_single_gpu_line_is_lean_and_dumps_what_the_oracle_computes(tmp_path):
+    """Without --full the N = 1 line is set-up, warm-up, the timed sweeps and the line; --dump-outputs then holds the output
+    arrays after the last timed sweep -- on this small domain whole, over the domain's own extents -- which must be the
+    oracle's bits after the same W + K sweeps from the same seeded inputs."""
+    import numpy as np
+    import __graft_entry__ as g
+    ni, nk, nj, steps, warmup = 96, 20, 40, 4, 2
+    out = _run(["--ni", str(ni), "--nk", str(nk), "--nj", str(nj), "--steps", str(steps), "--warmup", str(warmup),
+                "--dump-outputs", str(tmp_path)])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in out, key
+    assert out["steps"] == steps and len(out["per_sweep_ms"]) == steps and out["ms_per_step"] > 0
+    assert out["verified_vs_oracle"] is None
+    for key in ("cpu_baseline", "wrf_rows", "gpu_state"):
+        assert key not in out, key
+    assert "box_copy_GBps" not in out["roofline"] and "traffic_same_run_error" not in out["roofline"]
+    pkg, oracle = g.load_package(), g.load_oracle()
+    host = pkg.synth.make_patch(pkg.synth.domain_bounds(ni, nk, nj), pkg.GridConfig(), dtype=np.float64, seed=12345)
+    for _ in range(warmup + steps):
+        oracle.advance_mu_t(*host.args())
+    assert sorted(p.name for p in tmp_path.iterdir()) == sorted(f"{n}.npy" for n in pkg.synth.OUTPUTS)
+    for n in pkg.synth.OUTPUTS:
+        got = np.load(tmp_path / f"{n}.npy")
+        assert got.dtype == np.float64 and got.shape == host.arrays[n].shape, n
+        assert np.array_equal(got.view(np.uint8), host.arrays[n].view(np.uint8)), n
