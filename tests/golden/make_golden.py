@@ -15,6 +15,9 @@ lie into oracle/_ref/ (oracle/Makefile `ref`; nothing is copied into the reposit
 * golden_digests.json  -- sha256 of every input and output array of every case (incl. 64x40x64)
 * extra_reference_digests.json -- sha256 of every array after the reference's call on the random
                           extra cases of tests/cases.py (extra_case), fp32 and fp64
+* hard_inputs_digests.json -- sha256 of the 7 outputs (and of the 4 vertical metrics going in) of every
+                          shape of cases.SHAPES plus a tall sub-tile, every flag combination, fp32 and fp64,
+                          with the WRF-like metrics and each scalar set of tests/hard_inputs.py
 
 The reference ships no golden vectors of its own (its drivers diff against an absent
 /data2/... directory), so these are the pinned known answers.
@@ -32,6 +35,7 @@ sys.path.insert(0, str(ROOT / "tests"))
 
 import __graft_entry__ as g  # noqa: E402
 import cases  # noqa: E402
+import hard_inputs  # noqa: E402
 
 
 FULL_SHAPES = ("37x5x11_ragged", "130x3x7_tile", "70x1x9_onelevel")   # stored as full arrays
@@ -59,6 +63,7 @@ def main():
     (HERE / "golden_digests.json").write_text(json.dumps(digests, indent=1, sort_keys=True))
     print(f"wrote {len(small)} arrays, {len(digests)} cases")
     extra_reference_digests(pkg, oracle)
+    hard_inputs_digests(pkg, oracle)
 
 
 def extra_reference_digests(pkg, oracle):
@@ -73,6 +78,19 @@ def extra_reference_digests(pkg, oracle):
         extra[np.dtype(dtype).name] = recs
     (HERE / "extra_reference_digests.json").write_text(json.dumps(extra, indent=1, sort_keys=True))
     print(f"wrote {sum(len(v) for v in extra.values())} extra cases")
+
+
+def hard_inputs_digests(pkg, oracle):
+    recs = {}
+    for key in hard_inputs.hard_keys():
+        shape, flag, dtname, sset = key.split("/")
+        p = hard_inputs.hard_case(pkg, shape, flag, np.dtype(dtname), sset)
+        metrics = {n: cases.digest(p.arrays[n]) for n in hard_inputs.RANK1}
+        oracle.ref_advance_mu_t(*p.args())
+        recs[key] = {"bounds": list(p.bounds.as_tuple()), "scalars": [p.rdx, p.rdy, p.dts, p.epssm], "metrics": metrics,
+                     "outputs": {n: cases.digest(p.arrays[n]) for n in pkg.synth.OUTPUTS}}
+    (HERE / "hard_inputs_digests.json").write_text(json.dumps(recs, indent=0, sort_keys=True))
+    print(f"wrote {len(recs)} hard-input cases")
 
 
 if __name__ == "__main__":

@@ -99,7 +99,8 @@ def slab_mismatches(pkg, oracle, tmp_path, world, dims, dtype, sweeps, *, specif
 
 
 def run_grid_ranks(tmp_path, pi, pj, dims, *, dtype="f64", sweeps=2, overlap=True, specified=False, align=32, host_wait="1",
-                   static_inputs=False, fault=None, extra_env=None):
+                   static_inputs=False, fault=None, extra_env=None, hard=None):
+    """``hard``: a name of hard_inputs.SCALAR_SETS -- every rank steps with those scalars and hard_inputs' vertical metrics."""
     env = _rank_env(f"grid-{tmp_path.name}", dict(extra_env or {}, AMT_IPC_HOST_WAIT=host_wait), fault)
     procs = []
     for r in range(pi * pj):
@@ -108,17 +109,22 @@ def run_grid_ranks(tmp_path, pi, pj, dims, *, dtype="f64", sweeps=2, overlap=Tru
         cmd += [] if overlap else ["--no-overlap"]
         cmd += ["--specified"] if specified else []
         cmd += ["--static-inputs"] if static_inputs else []
+        cmd += ["--hard", hard] if hard else []
         procs.append(subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
     outs = _communicate(procs, "rank")
     assert [p.returncode for p in procs] == [0] * (pi * pj), "\n".join(outs)
     return outs
 
 
-def grid_mismatches(pkg, oracle, tmp_path, pi, pj, dims, dtype, sweeps, specified, align, *, seed=17, static_inputs=False):
+def grid_mismatches(pkg, oracle, tmp_path, pi, pj, dims, dtype, sweeps, specified, align, *, seed=17, static_inputs=False,
+                    hard=None):
     S = pkg.synth
     np_dtype = np.float64 if dtype == "f64" else np.float32
     gb = S.domain_bounds(*dims)
     full = S.make_patch(gb, pkg.GridConfig(specified=specified), dtype=np_dtype, seed=seed, global_dims=dims)
+    if hard:
+        import hard_inputs
+        hard_inputs.apply(full, hard_inputs.levels_for(full, hard_inputs.LEVEL_SEED), hard_inputs.SCALAR_SETS[hard])
     oracle_sweeps(pkg, oracle, full, seed, sweeps, refresh=not static_inputs)
     bad = []
     for r in range(pi * pj):

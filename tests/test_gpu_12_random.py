@@ -159,3 +159,56 @@ def test_cases_found_by_the_campaigns_stay_fixed(pkg, oracle, case):
                 assert bits_equal(got.arrays[n], want.arrays[n]), (case, variant, n, L.amt_march_last_kernel().decode())
     finally:
         L.amt_march_force_shape(0, 0, 0, -1, 1, 0, 0)
+
+
+N_HARD_CASES = int(os.environ.get("AMT_HARD_RANDOM_CASES", "500"))
+HARD_SEED = int(os.environ.get("AMT_HARD_RANDOM_SEED", "20261016"))
+
+
+def test_random_cases_on_wrf_levels_and_random_scalars(pkg, oracle):
+    """A second campaign on inputs without the generator's symmetries (tests/hard_inputs.py): every case gets WRF-like vertical
+    metrics of its own and scalars drawn from continuous ranges (rdx and rdy of grids from 300 m to 30 km, dx == dy in one case
+    of five, dts_rk of 0.2 to 20 s, any epssm).  Its own RNG stream: the campaign above is untouched."""
+    import torch
+    import hard_inputs as H
+    torch.cuda.set_device(0)
+    rng = np.random.default_rng(HARD_SEED)
+    S = pkg.synth
+    L = pkg.load_library()
+    ran = {"march": 0, "column": 0, "oneshot": 0}
+    try:
+        for case in range(N_HARD_CASES):
+            b, cfg, dtype, dims = random_case(pkg, rng)
+            rdx = 1.0 / rng.uniform(300.0, 30000.0)
+            scalars = dict(rdx=rdx, rdy=rdx if rng.random() < 0.2 else 1.0 / rng.uniform(300.0, 30000.0),
+                           dts=rng.uniform(0.2, 20.0), epssm=rng.uniform(0.0, 1.0))
+            host = S.make_patch(b, cfg, dtype=dtype, seed=5000 + case, global_dims=dims)
+            H.apply(host, H.levels_for(host, case), scalars)
+            want = host.copy()
+            oracle.advance_mu_t(*want.args())
+            what = (f"hard case {case}: bounds={b.as_tuple()} flags={cfg} dtype={np.dtype(dtype).name} "
+                    f"scalars={(host.rdx, host.rdy, host.dts, host.epssm)}")
+            L.amt_march_force_shape(0, 0, 0, -1, 0 if case % 5 == 4 else 1, 0, 0)
+            for variant, name in ((pkg.VARIANT_MARCH, "march"), (pkg.VARIANT_COLUMN, "column")):
+                dev = host.to_device("cuda:0")
+                try:
+                    pkg.advance_mu_t(*dev.args(), variant=variant)
+                except pkg.AmtError as e:
+                    if variant == pkg.VARIANT_MARCH and e.status == 3:
+                        continue                    # no march shape for this level count
+                    raise AssertionError(f"{what}: {e}")
+                torch.cuda.synchronize()
+                got = dev.to_host()
+                for n in S.FIELD_NAMES:
+                    assert bits_equal(got.arrays[n], want.arrays[n]), f"{what}: {name} kernel, {n} differs"
+                ran[name] += 1
+            if case % 4 == 0:
+                one = host.copy()
+                pkg.advance_mu_t(*one.args())
+                for n in S.FIELD_NAMES:
+                    assert bits_equal(one.arrays[n], want.arrays[n]), f"{what}: one-shot, {n} differs"
+                ran["oneshot"] += 1
+    finally:
+        L.amt_march_force_shape(0, 0, 0, -1, 1, 0, 0)
+    print("hard-input random campaign:", {"seed": HARD_SEED, "cases": N_HARD_CASES, "ran": ran})
+    assert ran["march"] >= N_HARD_CASES * 0.8 and ran["column"] >= N_HARD_CASES * 0.95

@@ -13,6 +13,7 @@ import numpy as np
 
 ROOT = Path(__file__).resolve().parent.parent.parent
 sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))
 
 
 def main():
@@ -28,6 +29,8 @@ def main():
     ap.add_argument("--specified", action="store_true")
     ap.add_argument("--align", type=int, default=32)
     ap.add_argument("--static-inputs", action="store_true", help="the inputs of sweep 1 for every sweep (see slab_ipc_rank.py)")
+    ap.add_argument("--hard", default=None, metavar="SET",
+                    help="tests/hard_inputs.py: its vertical metrics and the scalars of SCALAR_SETS[SET] instead of the generator's")
     a = ap.parse_args()
     import torch
     import __graft_entry__ as g
@@ -46,6 +49,9 @@ def main():
     with torch.cuda.stream(stream):
         dev = S.make_patch(pb, cfg, dtype=dtype, seed=a.seed, global_dims=dims, device="cuda:0")
         arr = dev.arrays
+        if a.hard:
+            import hard_inputs
+            hard_inputs.apply(dev, hard_inputs.levels_for(dev, hard_inputs.LEVEL_SEED), hard_inputs.SCALAR_SETS[a.hard])
         S.poison_halos(dev, S.neighbour_sides(ri, rj, pi, pj))
     torch.cuda.synchronize()
     st = pkg.patch.NativeGridStepper(dev, ri, rj, pi, pj, bytes(uid), stream=stream, overlap=not a.no_overlap, transport="ipc")
