@@ -512,6 +512,96 @@ int amt_march_set_beside(int rounds, int reserve_cus);
  * AMT_MARCH_NT in the environment sets the same at load time. */
 int amt_march_set_stream_policy(int policy);
 
+/* ------------------------------------------------------------------------
+ * (8) Ensembles: `members` patches of ONE shape -- same 17 bounds, same three flags, same four scalars rdx, rdy, dts, epssm,
+ *     same four 1-D metric arrays dnw, fnm, fnp, rdnw, different state -- advanced by ONE launch per sweep.  A patch of a few
+ *     hundred columns on a side cannot fill the chip on its own (128 x 128 columns: 256 blocks of one row, no reuse of the
+ *     j faces); 20-50 such members planned together can (measured: profiles/ensemble_notes.md).
+ *     LAYOUT: every 3-D and 2-D array has one more, slowest, dimension:
+ *       3-D: element (i,k,j,m) at ((m*jdim + (j-jms))*kdim + (k-kms))*idim + (i-ims)
+ *       2-D: element (i,j,m)   at  (m*jdim + (j-jms))*idim + (i-ims)               m = 0 .. members-1, jdim = jme-jms+1
+ *     i.e. Fortran u(ims:ime, kms:kme, jms:jme, 1:members), numpy / torch shape (members, jdim, kdim, idim) and
+ *     (members, jdim, idim).  Each member keeps its own halo rows jms..jts-1, jte+1..jme; nothing is shared between members
+ *     and nothing of one member is ever read for another.  Outputs outside each member's compute window keep the caller's
+ *     contents, as for a single patch.  Every member gets the bits the single-patch call gives that member alone.
+ *     NOT provided: pointer tables, members of different shapes or scalars, placement sampling, slabs / grids over an
+ *     ensemble (amt_slab_*, amt_grid_*), and a one-shot HOST-array ensemble call.
+ * ------------------------------------------------------------------------ */
+/* The device-resident drop-in (2) for an ensemble: the array pointers are the bases of the member-stacked device arrays, the
+ * 1-D arrays and the scalars are the shared ones.  Asynchronous on hip_stream; same preconditions and status codes as
+ * amt_advance_mu_t_device_*; members < 1 is AMT_ERR_INVALID_ARG. */
+int amt_advance_mu_t_ensemble_device_f32(
+    void *hip_stream, int variant, int members,
+    float *ww, const float *ww_1, const float *u, const float *u_1,
+    const float *v, const float *v_1,
+    float *mu, const float *mut, float *muave, float *muts,
+    const float *muu, const float *muv,
+    float *mudf, float *t, const float *t_1,
+    float *t_ave, const float *ft, const float *mu_tend,
+    float rdx, float rdy, float dts, float epssm,
+    const float *dnw, const float *fnm, const float *fnp, const float *rdnw,
+    const float *msfuy, const float *msfvx_inv,
+    const float *msftx, const float *msfty,
+    int periodic_x, int specified, int nested,
+    int ids, int ide, int jds, int jde, int kde,
+    int ims, int ime, int jms, int jme, int kms, int kme,
+    int its, int ite, int jts, int jte, int kts, int kte);
+
+int amt_advance_mu_t_ensemble_device_f64(
+    void *hip_stream, int variant, int members,
+    double *ww, const double *ww_1, const double *u, const double *u_1,
+    const double *v, const double *v_1,
+    double *mu, const double *mut, double *muave, double *muts,
+    const double *muu, const double *muv,
+    double *mudf, double *t, const double *t_1,
+    double *t_ave, const double *ft, const double *mu_tend,
+    double rdx, double rdy, double dts, double epssm,
+    const double *dnw, const double *fnm, const double *fnp, const double *rdnw,
+    const double *msfuy, const double *msfvx_inv,
+    const double *msftx, const double *msfty,
+    int periodic_x, int specified, int nested,
+    int ids, int ide, int jds, int jde, int kde,
+    int ims, int ime, int jms, int jme, int kms, int kme,
+    int its, int ite, int jts, int jte, int kts, int kte);
+
+/* Resident ensemble handle, the counterpart of amt_domain (3): owns (create) or adopts (wrap: fields[f] = base of the stacked
+ * device array of field f, all AMT_F_COUNT of them; hip_stream NULL = a stream of its own; nothing is copied, destroy frees
+ * nothing of the caller's) the member-stacked arrays, a stream and the scalars.  The four 1-D fields hold kdim elements. */
+typedef struct amt_ensemble amt_ensemble;
+int amt_ensemble_create(amt_ensemble **out, int members, int dtype_bytes,
+                        int periodic_x, int specified, int nested,
+                        int ids, int ide, int jds, int jde, int kde,
+                        int ims, int ime, int jms, int jme, int kms, int kme,
+                        int its, int ite, int jts, int jte, int kts, int kte);
+int amt_ensemble_wrap(amt_ensemble **out, int members, int dtype_bytes,
+                      int periodic_x, int specified, int nested,
+                      int ids, int ide, int jds, int jde, int kde,
+                      int ims, int ime, int jms, int jme, int kms, int kme,
+                      int its, int ite, int jts, int jte, int kts, int kte,
+                      void *const *fields, void *hip_stream);
+int amt_ensemble_destroy(amt_ensemble *e);
+int amt_ensemble_set_scalars(amt_ensemble *e, double rdx, double rdy, double dts, double epssm);
+int amt_ensemble_set_variant(amt_ensemble *e, int variant);
+int amt_ensemble_members(const amt_ensemble *e);                   /* 0 for NULL */
+/* ONE member (0-based) of a field; `host` holds that member in the single-patch layout of (3): the member's halo rows
+ * included, no other member touched.  A 1-D field is shared: `member` only has to name a member.  Synchronous. */
+int amt_ensemble_upload_member(amt_ensemble *e, int field, int member, const void *host);
+int amt_ensemble_download_member(amt_ensemble *e, int field, int member, void *host);
+/* member m is filled as amt_domain_fill_synthetic(seed + m, ...) fills a single patch; asynchronous on the handle's stream */
+int amt_ensemble_fill_synthetic(amt_ensemble *e, uint64_t seed,
+                                long gi0, long gk0, long gj0,
+                                long gidim, long gkdim, long gjdim);
+int amt_ensemble_step(amt_ensemble *e, int n_sweeps);              /* n_sweeps launches, each over all members; asynchronous */
+int amt_ensemble_step_timed(amt_ensemble *e, int n_sweeps, float *ms_total);
+int amt_ensemble_sync(amt_ensemble *e);
+void *amt_ensemble_field_ptr(amt_ensemble *e, int field);          /* base of the stacked device array, NULL on error */
+void *amt_ensemble_stream(amt_ensemble *e);                        /* hipStream_t */
+/* amt_march_rows_for for an ensemble: `members` x `ntile_i` tile columns of `nj` rows each in one launch; a block never
+ * leaves its member (the result is at most nj) and `max_rows` bounds the 32-bit offsets of ONE block.  members = 1 gives
+ * exactly amt_march_rows_for; 0 when there is nothing to plan.  amt_march_last_kernel of an ensemble launch ends in
+ * "jrows=R members=M jblocks=B" (B row blocks per member). */
+int amt_march_rows_for_members(long ntile_i, int members, int nj, int cus, long max_rows, int wbytes, int hl);
+
 #ifdef __cplusplus
 }
 #endif

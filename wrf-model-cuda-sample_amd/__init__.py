@@ -9,6 +9,8 @@ Host-side mirror of the reference's interface for this one path:
 * ``GridConfig``         -- the three ``grid_config_rec_type`` logicals the routine reads.
 * ``synth``              -- seeded WRF-shaped synthetic inputs (host and device fill).
 * ``wrfdump``            -- the reference drivers' big-endian per-variable dump format.
+* ``ensemble``           -- ``members`` same-shape patches advanced by one launch per sweep
+  (``advance_mu_t_ensemble``, ``Ensemble``; member-stacked arrays).
 * ``patch``              -- resident device patch (torch-allocated arrays) and j-slab
   decomposition with the one-row input-halo exchange over torch.distributed (RCCL).
 
@@ -25,3 +27,5 @@ from .api import host_set_devices, host_devices  # noqa: F401
 from . import synth  # noqa: F401
 from . import patch  # noqa: F401
 from . import wrfdump  # noqa: F401
+from . import ensemble  # noqa: F401
+from .ensemble import Ensemble, advance_mu_t_ensemble  # noqa: F401

@@ -121,6 +121,8 @@ int amt_build_params(const AmtArgs<T> &a, AmtParams<T> &p, AmtWindow &w, bool *e
     p.k1 = 1 - a.kms;
     p.nk = w.k_end;            // levels 1..k_end (k_end may be 0)
     p.edges = 0;
+    p.members = 0;             // a single patch; amt_device_call_ensemble sets the member count
+    p.jdim = a.jme - a.jms + 1;
     return AMT_OK;
 }
 
@@ -196,6 +198,23 @@ int amt_device_call(void *hip_stream, int variant, const AmtArgs<T> &a)
     return amt_launch<T>(static_cast<hipStream_t>(hip_stream), variant, p);
 }
 
+// `members` same-shape patches stacked along one more, slowest, dimension in every 3-D and 2-D array, as one launch
+// (amt_ensemble.hip).  Bounds, flags, scalars and the 1-D arrays are those of ONE member.
+template <typename T>
+int amt_device_call_ensemble(void *hip_stream, int variant, int members, const AmtArgs<T> &a)
+{
+    if (members < 1) return amt_fail(AMT_ERR_INVALID_ARG, "members = %d: an ensemble has at least one member", members);
+    AmtParams<T> p;
+    AmtWindow w;
+    bool empty = false;
+    int rc = amt_build_params(a, p, w, &empty);
+    if (rc != AMT_OK || empty) return rc;
+    if ((long)members * p.jdim > 0x7fffffffL)
+        return amt_fail(AMT_ERR_PRECONDITION, "%d members of %d rows: the stacked arrays have more than 2^31 - 1 rows", members, p.jdim);
+    p.members = members;
+    return amt_launch<T>(static_cast<hipStream_t>(hip_stream), variant, p);
+}
+
 // The same launch when another stream's kernels are to run beside it (amt_slab.hip: the interior rows of a j-slab
 // while the halo exchange and the edge rows go through the communication stream).
 template <typename T>
@@ -217,6 +236,8 @@ template int amt_device_call<double>(void *, int, const AmtArgs<double> &);
 template int amt_device_call_shared<float>(void *, int, const AmtArgs<float> &);
 template int amt_device_call_shared<double>(void *, int, const AmtArgs<double> &);
 template int amt_device_call_edges<float>(void *, int, const AmtArgs<float> &);
+template int amt_device_call_ensemble<float>(void *, int, int, const AmtArgs<float> &);
+template int amt_device_call_ensemble<double>(void *, int, int, const AmtArgs<double> &);
 template int amt_device_call_edges<double>(void *, int, const AmtArgs<double> &);
 
 extern "C" int amt_advance_mu_t_device_f32(void *hip_stream, int variant, AMT_SIG(float))

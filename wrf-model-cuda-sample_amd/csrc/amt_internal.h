@@ -75,6 +75,10 @@ extern template int amt_device_call<double>(void *, int, const AmtArgs<double> &
 template <typename T> int amt_device_call_shared(void *hip_stream, int variant, const AmtArgs<T> &a);
 extern template int amt_device_call_shared<float>(void *, int, const AmtArgs<float> &);
 extern template int amt_device_call_shared<double>(void *, int, const AmtArgs<double> &);
+// `members` patches of these bounds, member-stacked arrays, one launch (amt_ensemble.hip)
+template <typename T> int amt_device_call_ensemble(void *hip_stream, int variant, int members, const AmtArgs<T> &a);
+extern template int amt_device_call_ensemble<float>(void *, int, int, const AmtArgs<float> &);
+extern template int amt_device_call_ensemble<double>(void *, int, int, const AmtArgs<double> &);
 extern template int amt_device_call_edges<float>(void *, int, const AmtArgs<float> &);
 extern template int amt_device_call_edges<double>(void *, int, const AmtArgs<double> &);
 

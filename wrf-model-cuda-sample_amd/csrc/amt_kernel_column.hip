@@ -29,22 +29,27 @@
 // A workgroup is up to AMT_COLUMN_ROWS waves (blockDim.x / 64: the launcher's choice): wave w takes row (blockIdx / ntile_i) * rows + w of the tile.  The waves do not talk to each
 // other; they share a compute unit and an XCD, so the rows j-1, j+1 a wave reads (t_1, v, v_1) are its siblings' own rows: fetched
 // once into that L2 instead of once per row from HBM (profiles/r06_tall_columns.md).
+// Ensembles (AmtParams::members > 1): the row blocks of member m follow those of member m - 1, `njblk` row blocks per member, so a
+// workgroup never holds rows of two members and the halo rows between members are never computed; a single patch is the one-member case.
 #ifndef AMT_COLUMN_ROWS
 #define AMT_COLUMN_ROWS 4
 #endif
 
 template <typename T, bool RECOMPUTE>
-__global__ __launch_bounds__(64 * AMT_COLUMN_ROWS) void amt_column_kernel(const AmtParams<T> p, const int ntile_i)
+__global__ __launch_bounds__(64 * AMT_COLUMN_ROWS) void amt_column_kernel(const AmtParams<T> p, const int ntile_i, const int njblk)
 {
     extern __shared__ __align__(16) unsigned char amt_smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     T *dv = reinterpret_cast<T *>(amt_smem) + (size_t)wave * (size_t)(p.nk > 0 ? p.nk : 1) * 64;     // [nk][64] per wave (unused with RECOMPUTE)
 
     const int tile = blockIdx.x % ntile_i;
-    const int jrow = (blockIdx.x / ntile_i) * (int)(blockDim.x >> 6) + wave;
+    const int jblk = blockIdx.x / ntile_i;
+    const int mem  = jblk / njblk;                    // member (0 for a single patch)
+    const int jrow = (jblk - mem * njblk) * (int)(blockDim.x >> 6) + wave;
     const int ii   = tile * 64 + lane;                // zero-based memory i
-    const int jj   = p.j0 + jrow;                     // zero-based memory j
-    if (jj > p.j1 || ii < p.i0 || ii > p.i1) return;
+    const int jm   = p.j0 + jrow;                     // zero-based memory j within the member
+    if (jm > p.j1 || ii < p.i0 || ii > p.i1) return;
+    const int jj   = jm + mem * p.jdim;               // row of the member-stacked arrays
 
     const long idim = p.idim;
     const long js   = p.jstride;
@@ -145,12 +150,14 @@ hipError_t amt_launch_column(hipStream_t stream, const AmtParams<T> &p)
     const size_t lds = (size_t)(p.nk > 0 ? p.nk : 1) * 64 * sizeof(T);      // of ONE wave's dvdxi column
     // one dvdxi column per lane in LDS: 160 KB hold 320 levels in fp64, 640 in fp32 (the header's level limit)
     if (lds > 160 * 1024) return hipErrorInvalidConfiguration;
-    auto grid_for = [&](int rows) { return (unsigned)((long)ntile_i * ((nj + rows - 1) / rows)); };
+    const int members = p.members > 1 ? p.members : 1;
+    auto blocks_for = [&](int rows) { return (nj + rows - 1) / rows; };                // row blocks of ONE member
+    auto grid_for = [&](int rows) { return (unsigned)((long)ntile_i * blocks_for(rows) * members); };
     // tall columns: nothing in LDS, dvdxi evaluated twice (see the head of this file); AMT_COLUMN_RECOMPUTE=0|1 forces either
     const char *force = getenv("AMT_COLUMN_RECOMPUTE");          // read per launch: a test flips it in-process
     const bool recompute = force && *force ? atoi(force) != 0 : lds > 16 * 1024;
     if (recompute) {
-        hipLaunchKernelGGL((amt_column_kernel<T, true>), dim3(grid_for(AMT_COLUMN_ROWS)), dim3(64 * AMT_COLUMN_ROWS), 0, stream, q, ntile_i);
+        hipLaunchKernelGGL((amt_column_kernel<T, true>), dim3(grid_for(AMT_COLUMN_ROWS)), dim3(64 * AMT_COLUMN_ROWS), 0, stream, q, ntile_i, blocks_for(AMT_COLUMN_ROWS));
         return hipGetLastError();
     }
     // the LDS flavour: as many rows per workgroup as fit 64 KB of dvdxi columns (one where a single column is larger: the forced
@@ -169,7 +176,7 @@ hipError_t amt_launch_column(hipStream_t stream, const AmtParams<T> &p)
             granted |= 1u << (dev & 31);
         }
     }
-    hipLaunchKernelGGL((amt_column_kernel<T, false>), dim3(grid_for(rows)), dim3(64 * rows), lds * rows, stream, q, ntile_i);
+    hipLaunchKernelGGL((amt_column_kernel<T, false>), dim3(grid_for(rows)), dim3(64 * rows), lds * rows, stream, q, ntile_i, blocks_for(rows));
     return hipGetLastError();
 }
 

@@ -103,9 +103,13 @@ struct AmtMarchGrid {
     int col_lo;      // memory column of the first tile's column 0: the window's first column rounded down to a 128-B line
     int jrows;       // rows per workgroup
     int jstep;       // rows from one j block's first row to the next one's (jrows; edge launches: j1 - j0)
-    int njblk;       // number of j blocks
+    int njblk;       // number of j blocks (ensembles: of all members together)
     int nwg;         // ntile_i * njblk
     int xchunk;      // consecutive logical ids an XCD takes per round of the launch (0: one run for the whole launch)
+    // Ensembles: logical id -> (member, j block within the member, i tile), tile fastest.  A single patch
+    // is the one-member case: mjblk = njblk, mrows = 0 give the mapping it always had.
+    int mjblk;       // j blocks of ONE member
+    int mrows;       // rows from one member's first row to the next member's (its jdim; 0 for a single patch)
 };
 
 // ---------------------------------------------------------------------------
@@ -369,8 +373,13 @@ __global__ __launch_bounds__(WM * 64) void amt_march_kernel(const AmtParams<T> p
         const int base = whole * nx * xc, rest = g.nwg - base, q = rest / nx, r = rest % nx;
         lid = base + x * q + (x < r ? x : r) + (y - whole * xc);              // XCD x owns q (+1 if x < r) consecutive ids
     }
-    const int ja = p.j0 + (lid / g.ntile_i) * g.jstep;
-    const int jb = (ja + g.jrows - 1 < p.j1) ? ja + g.jrows - 1 : p.j1;
+    // (member, j block within the member): a block never runs across a member boundary, and its last row is clipped at the
+    // MEMBER's last window row -- the halo rows between two members are nobody's rows.  Wave-uniform integers, once per block.
+    const int jblk = lid / g.ntile_i, mem = jblk / g.mjblk;
+    const int mrow = mem * g.mrows;                                            // the member's row 0 in the stacked arrays
+    const int ja = p.j0 + mrow + (jblk - mem * g.mjblk) * g.jstep;
+    const int j1 = p.j1 + mrow;
+    const int jb = (ja + g.jrows - 1 < j1) ? ja + g.jrows - 1 : j1;
     // Tiles are anchored at the WINDOW (its first column rounded down to a 128-byte line of the row), not
     // at multiples of TC from the row start: a window that starts 32 elements into a row (the resident
     // layout) would otherwise straddle one more, half-empty tile (512x60x512: 9 x 27 = 243 workgroups on
@@ -1193,6 +1202,18 @@ extern "C" int amt_march_rows_for(long ntile_i, int nj, int cus, long max_rows, 
     return amt_march_rows(ntile_i, nj, cus, max_rows, amt_march_rows_cap(wbytes, hl), 1, nullptr, nullptr);
 }
 
+// The same for an ensemble of `members` patches of that shape stepped as ONE launch: the launch holds
+// members * ntile_i tile columns of nj rows each, and a block never leaves its member (r <= nj); max_rows bounds the 32-bit
+// offsets of ONE block (a member's base is part of the block's 64-bit base).  members = 1 is amt_march_rows_for.
+extern "C" int amt_march_rows_for_members(long ntile_i, int members, int nj, int cus, long max_rows, int wbytes, int hl)
+{
+    if (members < 1) return 0;
+    return amt_march_rows_for(ntile_i * (long)members, nj, cus, max_rows, wbytes, hl);
+}
+
+// members of a call as the plan counts them (0, a single-patch call, is one member)
+template <typename T> static int amt_march_members(const AmtParams<T> &p) { return p.members > 1 ? p.members : 1; }
+
 // Shape preference.  Measured (profiles/r02_shapes.md): most waves to hide latency and fewest
 // registers per lane first -- 4 levels per lane is what fits 127 VGPRs in fp64 (and in fp32 with two
 // columns per lane) without scratch; more levels come from splitting the wave into level groups
@@ -1282,7 +1303,7 @@ template <typename T> static bool amt_march_pick(const AmtParams<T> &p, AmtMarch
                 const int tc = (64 / q.hl) * q.vw;
                 double c = 0;
                 long rounds = 1;
-                amt_march_rows((p.i1 - amt_march_col_lo(p)) / tc + 1, nj, amt_march_plan_cus(cus, p.edges), amt_march_max_rows(p), amt_march_rows_cap((int)sizeof(T), q.hl), p.edges == 2 ? amt_march_env().beside_rounds : 1, &c, &rounds);
+                amt_march_rows((long)((p.i1 - amt_march_col_lo(p)) / tc + 1) * amt_march_members(p), nj, amt_march_plan_cus(cus, p.edges), amt_march_max_rows(p), amt_march_rows_cap((int)sizeof(T), q.hl), p.edges == 2 ? amt_march_env().beside_rounds : 1, &c, &rounds);
                 return c * (q.hl == out.hl ? 1.0 : rounds == 1 ? 0.8 : 1.2);
             };
             if (out.hl < 4)
@@ -1305,6 +1326,7 @@ template <typename T> static bool amt_march_pick(const AmtParams<T> &p, AmtMarch
 template <typename T> struct AmtMarchPlan {
     // key
     int nk, idim, kdim, i0, i1, nj, dev, generation, edges;
+    int members, mrows;    // AmtParams::members as passed (0: single-patch call), rows between members (0 unless members > 1)
     bool dma_ok;
     // plan
     bool ok;
@@ -1353,16 +1375,21 @@ template <typename T> static bool amt_march_make_plan(const AmtParams<T> &p, Amt
     g.col_lo = amt_march_col_lo(p);
     g.ntile_i = (p.i1 - g.col_lo) / tc + 1;
     int jrows = env.jrows;
-    if (jrows < 1) jrows = amt_march_rows(g.ntile_i, nj, amt_march_plan_cus(amt_march_cus(pl.dev), p.edges), max_rows, amt_march_rows_cap((int)sizeof(T), s.hl), p.edges == 2 ? amt_march_env().beside_rounds : 1, nullptr, nullptr);
+    const int members = amt_march_members(p);
+    if (jrows < 1) jrows = amt_march_rows((long)g.ntile_i * members, nj, amt_march_plan_cus(amt_march_cus(pl.dev), p.edges), max_rows, amt_march_rows_cap((int)sizeof(T), s.hl), p.edges == 2 ? amt_march_env().beside_rounds : 1, nullptr, nullptr);
     if (jrows > nj) jrows = nj;
     if (jrows > max_rows) jrows = (int)max_rows;
     g.jrows = jrows;
     g.jstep = jrows;
     g.njblk = (nj + jrows - 1) / jrows;
+    g.mjblk = g.njblk;
+    g.mrows = members > 1 ? p.jdim : 0;
+    if ((long)g.ntile_i * g.njblk * members > 0x7fffffffL) return false;
+    g.njblk *= members;                              // the blocks of member m follow those of member m - 1
     if (p.edges == 1) {                              // rows j0 and j1 only: two one-row blocks
         g.jrows = 1;
         g.jstep = nj - 1;
-        g.njblk = 2;
+        g.njblk = g.mjblk = 2;
     }
     g.nwg = g.ntile_i * g.njblk;
     g.xchunk = env.xchunk > 0 ? env.xchunk : 0;
@@ -1382,6 +1409,10 @@ template <typename T> static bool amt_march_make_plan(const AmtParams<T> &p, Amt
         fprintf(stderr, "[amt march] nk %d idim %d window i %d..%d, %d rows -> %s %s: %d waves, %zu B LDS, %d tiles x %d blocks of %d rows\n",
                 p.nk, p.idim, p.i0, p.i1, nj, cached ? pl.entry->name_cached : pl.entry->name, pl.full ? "FULL" : "ragged", pl.nw, pl.lds, g.ntile_i, g.njblk, g.jrows);
     snprintf(pl.label, sizeof pl.label, "%s %s jrows=%d", cached ? pl.entry->name_cached : pl.entry->name, pl.full ? "FULL" : "ragged", g.jrows);
+    if (p.members >= 1) {                            // an ensemble call says so: members, and the j blocks each of them is cut into
+        const size_t n = strlen(pl.label);
+        snprintf(pl.label + n, sizeof pl.label - n, " members=%d jblocks=%d", p.members, g.mjblk);
+    }
     snprintf(g_march_last, sizeof g_march_last, "%s", pl.label);
     pl.ok = true;
     return true;
@@ -1396,10 +1427,12 @@ template <typename T> static const AmtMarchPlan<T> *amt_march_plan(const AmtPara
     if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
     const int nj = p.j1 - p.j0 + 1;
     const bool dma_ok = amt_march_dma_layout_ok(p);
+    const int mrows = p.members > 1 ? p.jdim : 0;
     for (int i = 0; i < used; ++i) {
         const AmtMarchPlan<T> &c = cache[i];
         if (c.nk == p.nk && c.idim == p.idim && c.kdim == p.kdim && c.i0 == p.i0 && c.i1 == p.i1 && c.nj == nj
-            && c.dev == dev && c.dma_ok == dma_ok && c.generation == g_march_generation && c.edges == p.edges)
+            && c.dev == dev && c.dma_ok == dma_ok && c.generation == g_march_generation && c.edges == p.edges
+            && c.members == p.members && c.mrows == mrows)
             return c.ok ? &c : nullptr;
     }
     const int slot = used < NSLOT ? used++ : (next = (next + 1) % NSLOT);
@@ -1407,6 +1440,7 @@ template <typename T> static const AmtMarchPlan<T> *amt_march_plan(const AmtPara
     c.nk = p.nk; c.idim = p.idim; c.kdim = p.kdim; c.i0 = p.i0; c.i1 = p.i1; c.nj = nj; c.dev = dev; c.dma_ok = dma_ok;
     c.generation = g_march_generation;
     c.edges = p.edges;
+    c.members = p.members; c.mrows = mrows;
     amt_march_make_plan(p, c);
     return c.ok ? &c : nullptr;
 }

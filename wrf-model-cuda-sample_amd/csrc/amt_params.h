@@ -25,6 +25,11 @@ struct AmtParams {
                            // 2: the whole window, launched BESIDE another stream's kernels (a j-slab's interior rows while its
                            //    halo exchange runs): planned in at least two rounds of workgroups, so that the other stream's
                            //    kernels get compute units at a round boundary instead of behind the whole launch
+    // Ensemble (amt_ensemble.hip): `members` same-shape patches lie one after the other in every 3-D and
+    // 2-D array, member m's row j being row m * jdim + j of a taller array; i0..i1, j0..j1 are the window of ONE member and the
+    // 1-D arrays and scalars are shared.  0: a single-patch call (planned and labelled as before); >= 1: an ensemble call.
+    int members;
+    int jdim;              // memory rows of one member (jme - jms + 1): the row distance from one member to the next
 };
 
 // Compute window, module_small_step_em.f90:91-106.

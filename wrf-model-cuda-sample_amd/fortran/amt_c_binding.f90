@@ -353,6 +353,154 @@ MODULE amt_c_binding
          integer(c_long), value :: idim, kdim, jdim, gi0, gk0, gj0, gidim, gkdim, gjdim
          integer(c_int) :: rc
       end function
+
+      ! (8) ensembles: `members` patches of one shape, every 3-D and 2-D array with one more, slowest, dimension --
+      ! u(ims:ime, kms:kme, jms:jme, 1:members), mu(ims:ime, jms:jme, 1:members) -- bounds, flags, scalars and the four 1-D
+      ! metric arrays shared; ONE launch per sweep
+      function amt_advance_mu_t_ensemble_device_f32(hip_stream, variant, members,                     &
+                                    ww, ww_1, u, u_1, v, v_1, mu, mut, muave, muts, muu, muv,    &
+                                    mudf, t, t_1, t_ave, ft, mu_tend, rdx, rdy, dts, epssm,      &
+                                    dnw, fnm, fnp, rdnw, msfuy, msfvx_inv, msftx, msfty,         &
+                                    periodic_x, specified, nested,                               &
+                                    ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,       &
+                                    its, ite, jts, jte, kts, kte)                                &
+            bind(C, name="amt_advance_mu_t_ensemble_device_f32") result(rc)
+         import :: c_ptr, c_float, c_int
+         type(c_ptr), value :: hip_stream                    ! hipStream_t, c_null_ptr = the default stream
+         integer(c_int), value :: variant, members
+         type(c_ptr), value :: ww, ww_1, u, u_1, v, v_1, mu, mut, muave, muts, muu, muv      ! DEVICE addresses, member-stacked
+         type(c_ptr), value :: mudf, t, t_1, t_ave, ft, mu_tend
+         real(c_float), value :: rdx, rdy, dts, epssm
+         type(c_ptr), value :: dnw, fnm, fnp, rdnw, msfuy, msfvx_inv, msftx, msfty           ! dnw .. rdnw: shared, kdim elements
+         integer(c_int), value :: periodic_x, specified, nested
+         integer(c_int), value :: ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme
+         integer(c_int), value :: its, ite, jts, jte, kts, kte
+         integer(c_int) :: rc
+      end function
+      function amt_advance_mu_t_ensemble_device_f64(hip_stream, variant, members,                     &
+                                    ww, ww_1, u, u_1, v, v_1, mu, mut, muave, muts, muu, muv,    &
+                                    mudf, t, t_1, t_ave, ft, mu_tend, rdx, rdy, dts, epssm,      &
+                                    dnw, fnm, fnp, rdnw, msfuy, msfvx_inv, msftx, msfty,         &
+                                    periodic_x, specified, nested,                               &
+                                    ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,       &
+                                    its, ite, jts, jte, kts, kte)                                &
+            bind(C, name="amt_advance_mu_t_ensemble_device_f64") result(rc)
+         import :: c_ptr, c_double, c_int
+         type(c_ptr), value :: hip_stream                    ! hipStream_t, c_null_ptr = the default stream
+         integer(c_int), value :: variant, members
+         type(c_ptr), value :: ww, ww_1, u, u_1, v, v_1, mu, mut, muave, muts, muu, muv      ! DEVICE addresses, member-stacked
+         type(c_ptr), value :: mudf, t, t_1, t_ave, ft, mu_tend
+         real(c_double), value :: rdx, rdy, dts, epssm
+         type(c_ptr), value :: dnw, fnm, fnp, rdnw, msfuy, msfvx_inv, msftx, msfty           ! dnw .. rdnw: shared, kdim elements
+         integer(c_int), value :: periodic_x, specified, nested
+         integer(c_int), value :: ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme
+         integer(c_int), value :: its, ite, jts, jte, kts, kte
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_create(handle, members, dtype_bytes, periodic_x, specified, nested,  &
+                                   ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,        &
+                                   its, ite, jts, jte, kts, kte) bind(C, name="amt_ensemble_create") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr) :: handle                      ! amt_ensemble **
+         integer(c_int), value :: members, dtype_bytes, periodic_x, specified, nested
+         integer(c_int), value :: ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme
+         integer(c_int), value :: its, ite, jts, jte, kts, kte
+         integer(c_int) :: rc
+      end function
+      ! over device arrays the caller owns: fields(0:25) = the bases of the member-stacked arrays in amt_field order
+      function amt_ensemble_wrap(handle, members, dtype_bytes, periodic_x, specified, nested,    &
+                                 ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,          &
+                                 its, ite, jts, jte, kts, kte, fields, hip_stream) bind(C, name="amt_ensemble_wrap") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr) :: handle                      ! amt_ensemble **
+         integer(c_int), value :: members, dtype_bytes, periodic_x, specified, nested
+         integer(c_int), value :: ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme
+         integer(c_int), value :: its, ite, jts, jte, kts, kte
+         type(c_ptr), intent(in) :: fields(*)
+         type(c_ptr), value :: hip_stream           ! c_null_ptr: a stream of the handle's own
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_destroy(handle) bind(C, name="amt_ensemble_destroy") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_set_scalars(handle, rdx, rdy, dts, epssm) bind(C, name="amt_ensemble_set_scalars") result(rc)
+         import :: c_ptr, c_int, c_double
+         type(c_ptr), value :: handle
+         real(c_double), value :: rdx, rdy, dts, epssm
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_set_variant(handle, variant) bind(C, name="amt_ensemble_set_variant") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: variant
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_members(handle) bind(C, name="amt_ensemble_members") result(n)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int) :: n
+      end function
+      ! ONE member (0-based) of a field; host holds that member in the single-patch layout (ims:ime[,kms:kme],jms:jme)
+      function amt_ensemble_upload_member(handle, field, member, host) bind(C, name="amt_ensemble_upload_member") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle, host
+         integer(c_int), value :: field, member
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_download_member(handle, field, member, host) bind(C, name="amt_ensemble_download_member") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle, host
+         integer(c_int), value :: field, member
+         integer(c_int) :: rc
+      end function
+      ! member m as amt_domain_fill_synthetic(seed + m, ...) fills a single patch
+      function amt_ensemble_fill_synthetic(handle, seed, gi0, gk0, gj0, gidim, gkdim, gjdim)      &
+            bind(C, name="amt_ensemble_fill_synthetic") result(rc)
+         import :: c_ptr, c_int, c_int64_t, c_long
+         type(c_ptr), value :: handle
+         integer(c_int64_t), value :: seed
+         integer(c_long), value :: gi0, gk0, gj0, gidim, gkdim, gjdim
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_step(handle, n_sweeps) bind(C, name="amt_ensemble_step") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: n_sweeps
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_step_timed(handle, n_sweeps, ms_total) bind(C, name="amt_ensemble_step_timed") result(rc)
+         import :: c_ptr, c_int, c_float
+         type(c_ptr), value :: handle
+         integer(c_int), value :: n_sweeps
+         real(c_float) :: ms_total
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_sync(handle) bind(C, name="amt_ensemble_sync") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_field_ptr(handle, field) bind(C, name="amt_ensemble_field_ptr") result(ptr)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: field
+         type(c_ptr) :: ptr
+      end function
+      function amt_ensemble_stream(handle) bind(C, name="amt_ensemble_stream") result(stream)
+         import :: c_ptr
+         type(c_ptr), value :: handle
+         type(c_ptr) :: stream
+      end function
+      ! rows per workgroup of an ensemble launch (host arithmetic; members = 1: the single patch's)
+      function amt_march_rows_for_members(ntile_i, members, nj, cus, max_rows, wbytes, hl)        &
+            bind(C, name="amt_march_rows_for_members") result(rows)
+         import :: c_int, c_long
+         integer(c_long), value :: ntile_i, max_rows
+         integer(c_int), value :: members, nj, cus, wbytes, hl
+         integer(c_int) :: rows
+      end function
    end interface
 
    ! enum amt_field (include/amt_synth.h): the Fortran argument order

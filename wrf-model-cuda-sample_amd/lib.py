@@ -36,8 +36,8 @@ _I = ctypes.c_int
 _L = ctypes.c_long
 
 
-def _adv_sig(real, device: bool):
-    head = [_P, _I] if device else []
+def _adv_sig(real, device: bool, ensemble: bool = False):
+    head = ([_P, _I] if device else []) + ([_I] if ensemble else [])      # stream, variant[, members]
     return head + [_P] * 18 + [real] * 4 + [_P] * 8 + [_I] * (3 + 17)
 
 
@@ -116,6 +116,23 @@ SYMBOLS = {
     "amt_grid_comm_info": (_I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "amt_grid_barrier": (_I, [_P]),
     "amt_grid_max": (_I, [_P, ctypes.POINTER(ctypes.c_double)]),
+    "amt_advance_mu_t_ensemble_device_f32": (_I, _adv_sig(ctypes.c_float, True, ensemble=True)),
+    "amt_advance_mu_t_ensemble_device_f64": (_I, _adv_sig(ctypes.c_double, True, ensemble=True)),
+    "amt_ensemble_create": (_I, [ctypes.POINTER(_P), _I, _I] + [_I] * 20),
+    "amt_ensemble_wrap": (_I, [ctypes.POINTER(_P), _I, _I] + [_I] * 20 + [ctypes.POINTER(_P), _P]),
+    "amt_ensemble_destroy": (_I, [_P]),
+    "amt_ensemble_set_scalars": (_I, [_P] + [ctypes.c_double] * 4),
+    "amt_ensemble_set_variant": (_I, [_P, _I]),
+    "amt_ensemble_members": (_I, [_P]),
+    "amt_ensemble_upload_member": (_I, [_P, _I, _I, _P]),
+    "amt_ensemble_download_member": (_I, [_P, _I, _I, _P]),
+    "amt_ensemble_fill_synthetic": (_I, [_P, ctypes.c_uint64] + [_L] * 6),
+    "amt_ensemble_step": (_I, [_P, _I]),
+    "amt_ensemble_step_timed": (_I, [_P, _I, ctypes.POINTER(ctypes.c_float)]),
+    "amt_ensemble_sync": (_I, [_P]),
+    "amt_ensemble_field_ptr": (_P, [_P, _I]),
+    "amt_ensemble_stream": (_P, [_P]),
+    "amt_march_rows_for_members": (_I, [ctypes.c_long, _I, _I, _I, ctypes.c_long, _I, _I]),
     "amt_march_force_shape": (_I, [_I] * 7),
     "amt_march_rows_for": (_I, [ctypes.c_long, _I, _I, ctypes.c_long, _I, _I]),
     "amt_march_set_xchunk": (_I, [_I]),
