@@ -384,7 +384,15 @@ int amt_synth_fill_device(void *hip_stream, int field, int dtype_bytes, void *ds
 enum amt_slab_flags {
     AMT_SLAB_NO_OVERLAP = 1,                 /* exchange, then all rows, on one stream          */
     AMT_SLAB_LOOPBACK = 2,                   /* one-rank test mode: both neighbours are this rank */
-    AMT_SLAB_TRANSPORT_IPC = 4               /* peer copies between processes instead of RCCL     */
+    AMT_SLAB_TRANSPORT_IPC = 4,              /* peer copies between processes instead of RCCL     */
+    /* Cyclic (periodic) domain, section (9): the decomposition is a torus in that direction.  With several ranks in it the edge
+     * ranks are each other's neighbours and the wrap columns / rows travel as ordinary segments of the same exchange (both
+     * transports, every schedule; counted by amt_*_halo_bytes); the edge ranks gather and scatter at their compute window's edge
+     * (a last patch may end at ide-1 or at ide).  With ONE rank in it (a j-slab world with CYCLIC_X, a world of one) no transport
+     * is involved: the refresh kernel of (9) runs on the domain's stream in front of every sweep.  Preconditions as in (9);
+     * together with AMT_SLAB_LOOPBACK: AMT_ERR_INVALID_ARG. */
+    AMT_SLAB_CYCLIC_X = 8,
+    AMT_SLAB_CYCLIC_Y = 16
 };
 typedef struct amt_slab amt_slab;
 
@@ -601,6 +609,54 @@ void *amt_ensemble_stream(amt_ensemble *e);                        /* hipStream_
  * exactly amt_march_rows_for; 0 when there is nothing to plan.  amt_march_last_kernel of an ensemble launch ends in
  * "jrows=R members=M jblocks=B" (B row blocks per member). */
 int amt_march_rows_for_members(long ntile_i, int members, int nj, int cus, long max_rows, int wbytes, int hl);
+
+/* ------------------------------------------------------------------------
+ * (9) Cyclic (periodic) lateral boundaries, refreshed on the device.  The routine reads one cell past its compute window
+ *     (i_start..i_end, j_start..j_end of amt_compute_window): column i_end+1 of u, u_1, t_1, muu, msfuy and column i_start-1
+ *     of t_1 (module_small_step_em.f90:145-146, :244-245), row j_end+1 of v, v_1, t_1, muv, msfvx_inv and row j_start-1 of t_1
+ *     (:143-144, :241-242).  periodic_x only widens the loop bounds (:97-102); in WRF the periodic-boundary exchange fills
+ *     those cells before every call.  For a patch that holds the whole period of a direction, these calls do:
+ *       AMT_CYCLIC_X, period ide - ids: column ide receives column ids of u, u_1, t_1, muu, msfuy; column ids-1 receives
+ *                     column ide-1 of t_1; rows j_start..j_end, every memory level kms..kme
+ *       AMT_CYCLIC_Y, period jde - jds: row jde receives row jds of v, v_1, t_1, muv, msfvx_inv; row jds-1 receives row
+ *                     jde-1 of t_1; columns i_start..i_end, every memory level
+ *     Corner cells are not written (the routine reads no diagonals), nothing outside the named cells changes, and the
+ *     elements move as bits (NaN payloads survive).  One launch does a whole refresh, for every member of an ensemble.
+ *     AMT_ERR_PRECONDITION: cyclic x with a clipped i window (it needs periodic_x || !(specified || nested)); cyclic y with
+ *     specified or nested; a window that does not span the period (the window decides, not ite / jte: a last patch may end at
+ *     ide-1 or at ide); memory extents that do not hold the destination cells.  axes = 0 refreshes nothing.
+ *     A domain split over ranks wraps through AMT_SLAB_CYCLIC_X / AMT_SLAB_CYCLIC_Y of (5) instead.
+ * ------------------------------------------------------------------------ */
+enum amt_cyclic_axes { AMT_CYCLIC_X = 1, AMT_CYCLIC_Y = 2 };
+/* pointer level, for callers of amt_advance_mu_t_device_* (members = 1) or amt_advance_mu_t_ensemble_device_* who keep
+ * their own arrays; asynchronous on hip_stream (NULL = the default stream).  Only the arrays of the chosen axes are touched
+ * (x: u, u_1, t_1, muu, msfuy; y: v, v_1, t_1, muv, msfvx_inv); the others may be NULL. */
+int amt_cyclic_fill_device_f32(
+    void *hip_stream, int axes, int members,
+    float *u, float *u_1, float *v, float *v_1, float *t_1,
+    float *muu, float *muv, float *msfuy, float *msfvx_inv,
+    int periodic_x, int specified, int nested,
+    int ids, int ide, int jds, int jde, int kde,
+    int ims, int ime, int jms, int jme, int kms, int kme,
+    int its, int ite, int jts, int jte, int kts, int kte);
+int amt_cyclic_fill_device_f64(
+    void *hip_stream, int axes, int members,
+    double *u, double *u_1, double *v, double *v_1, double *t_1,
+    double *muu, double *muv, double *msfuy, double *msfvx_inv,
+    int periodic_x, int specified, int nested,
+    int ids, int ide, int jds, int jde, int kde,
+    int ims, int ime, int jms, int jme, int kms, int kme,
+    int its, int ite, int jts, int jte, int kts, int kte);
+/* one refresh now; asynchronous on the handle's stream (wrapped handles: the caller's stream) */
+int amt_domain_cyclic_fill(amt_domain *d, int axes);
+/* 0 = off (the default); otherwise every sweep of amt_domain_step / amt_domain_step_timed is preceded by a refresh on the
+ * same stream.  A combination the handle's flags and extents do not admit is refused here and changes nothing. */
+int amt_domain_set_cyclic(amt_domain *d, int axes);
+int amt_domain_cyclic(const amt_domain *d);                        /* the axes set; 0 for NULL */
+/* the same for an ensemble: all members in one launch */
+int amt_ensemble_cyclic_fill(amt_ensemble *e, int axes);
+int amt_ensemble_set_cyclic(amt_ensemble *e, int axes);
+int amt_ensemble_cyclic(const amt_ensemble *e);
 
 #ifdef __cplusplus
 }

@@ -91,6 +91,38 @@ def bind_device_call(ww, ww_1, u, u_1, v, v_1, mu, mut, muave, muts, muu, muv, m
     return call
 
 
+CYCLIC_X, CYCLIC_Y = 1, 2         # enum amt_cyclic_axes
+
+
+def cyclic_fill(u, u_1, v, v_1, t_1, muu, muv, msfuy, msfvx_inv, config_flags,
+                ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,
+                its, ite, jts, jte, kts, kte, *, axes=CYCLIC_X | CYCLIC_Y, members=1, stream=None):
+    """Refresh the cyclic wrap cells of a patch's (``members`` > 1: a member-stacked ensemble's) torch device tensors in
+    place (``amt_cyclic_fill_device_f32/_f64``): column ide <- ids of u, u_1, t_1, muu, msfuy and column ids-1 <- ide-1 of t_1
+    (CYCLIC_X), row jde <- jds of v, v_1, t_1, muv, msfvx_inv and row jds-1 <- jde-1 of t_1 (CYCLIC_Y).  Asynchronous on
+    ``stream`` (default: torch's current).  Call it in front of ``advance_mu_t`` on the same stream."""
+    import torch
+    L = _lib.load_library()
+    arrays = (u, u_1, v, v_1, t_1, muu, muv, msfuy, msfvx_inv)
+    idim, kdim, jdim = ime - ims + 1, kme - kms + 1, jme - jms + 1
+    want = [jdim * kdim * idim] * 5 + [jdim * idim] * 4
+    dt = t_1.dtype
+    if dt not in (torch.float32, torch.float64):
+        raise TypeError(f"unsupported dtype {dt}")
+    for a, n in zip(arrays, want):
+        if not (_is_torch(a) and a.is_cuda and a.dtype == dt and a.is_contiguous() and a.numel() == n * int(members)):
+            raise TypeError("cyclic_fill needs contiguous CUDA tensors of one dtype and of the memory extents")
+    if stream is None:
+        stream = torch.cuda.current_stream(t_1.device)
+    handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+    fn = L.amt_cyclic_fill_device_f32 if dt == torch.float32 else L.amt_cyclic_fill_device_f64
+    with torch.cuda.device(t_1.device):
+        status = fn(ctypes.c_void_p(handle), int(axes), int(members), *[ctypes.c_void_p(a.data_ptr()) for a in arrays],
+                    *flags_as_ints(config_flags),
+                    *[int(x) for x in (ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte)])
+    _lib.check(status)
+
+
 def advance_mu_t(ww, ww_1, u, u_1, v, v_1, mu, mut, muave, muts, muu, muv, mudf, t, t_1,
                  t_ave, ft, mu_tend, rdx, rdy, dts, epssm, dnw, fnm, fnp, rdnw,
                  msfuy, msfvx_inv, msftx, msfty, config_flags,

@@ -323,11 +323,30 @@ static int amt_domain_step_t(amt_domain *d, int n_sweeps)
     AmtArgs<T> a;
     amt_domain_args<T>(d, a);
     for (int s = 0; s < n_sweeps; ++s) {
-        int rc = amt_device_call<T>(d->stream, d->variant, a);
+        // cyclic boundaries: the wrap cells are refreshed in front of every sweep, on the same stream (the inputs are final there)
+        int rc = d->cyclic ? amt_cyclic_refresh_domain("amt_domain_step", d, d->cyclic, 1) : AMT_OK;
+        if (rc == AMT_OK) rc = amt_device_call<T>(d->stream, d->variant, a);
         if (rc) return rc;
     }
     return AMT_OK;
 }
+
+extern "C" int amt_domain_cyclic_fill(amt_domain *d, int axes)
+{
+    if (!d) return amt_fail(AMT_ERR_INVALID_ARG, "null domain");
+    DeviceScope scope(d->device);
+    return amt_cyclic_refresh_domain("amt_domain_cyclic_fill", d, axes, 1);
+}
+
+extern "C" int amt_domain_set_cyclic(amt_domain *d, int axes)
+{
+    if (!d) return amt_fail(AMT_ERR_INVALID_ARG, "null domain");
+    const int rc = amt_cyclic_check_domain("amt_domain_set_cyclic", d, axes, 1);
+    if (rc == AMT_OK) d->cyclic = axes;
+    return rc;
+}
+
+extern "C" int amt_domain_cyclic(const amt_domain *d) { return d ? d->cyclic : 0; }
 
 extern "C" int amt_domain_step(amt_domain *d, int n_sweeps)
 {

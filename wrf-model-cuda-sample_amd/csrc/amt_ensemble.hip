@@ -178,11 +178,30 @@ static int amt_ensemble_step_t(amt_ensemble *e, int n_sweeps)
     AmtArgs<T> a;
     amt_domain_args<T>(&e->d, a);
     for (int s = 0; s < n_sweeps; ++s) {
-        int rc = amt_device_call_ensemble<T>(e->d.stream, e->d.variant, e->members, a);
+        // cyclic boundaries: every member's wrap cells in one launch in front of the sweep, on the same stream
+        int rc = e->d.cyclic ? amt_cyclic_refresh_domain("amt_ensemble_step", &e->d, e->d.cyclic, e->members) : AMT_OK;
+        if (rc == AMT_OK) rc = amt_device_call_ensemble<T>(e->d.stream, e->d.variant, e->members, a);
         if (rc) return rc;
     }
     return AMT_OK;
 }
+
+extern "C" int amt_ensemble_cyclic_fill(amt_ensemble *e, int axes)
+{
+    if (!e) return amt_fail(AMT_ERR_INVALID_ARG, "null ensemble");
+    DeviceScope scope(e->d.device);
+    return amt_cyclic_refresh_domain("amt_ensemble_cyclic_fill", &e->d, axes, e->members);
+}
+
+extern "C" int amt_ensemble_set_cyclic(amt_ensemble *e, int axes)
+{
+    if (!e) return amt_fail(AMT_ERR_INVALID_ARG, "null ensemble");
+    const int rc = amt_cyclic_check_domain("amt_ensemble_set_cyclic", &e->d, axes, e->members);
+    if (rc == AMT_OK) e->d.cyclic = axes;
+    return rc;
+}
+
+extern "C" int amt_ensemble_cyclic(const amt_ensemble *e) { return e ? e->d.cyclic : 0; }
 
 extern "C" int amt_ensemble_step(amt_ensemble *e, int n_sweeps)
 {

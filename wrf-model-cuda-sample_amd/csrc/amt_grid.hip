@@ -24,6 +24,11 @@ struct amt_grid {
     hipStream_t col_stream[2] = {nullptr, nullptr};         // the two boundary columns run beside the boundary rows
     hipEvent_t halos_in = nullptr, col_done[2] = {nullptr, nullptr};
     hipEvent_t inputs_final = nullptr, edges_done = nullptr, t0 = nullptr, t1 = nullptr;
+    // Cyclic boundaries (AMT_SLAB_CYCLIC_X / _Y).  wrap_*: the direction has several ranks and the edge
+    // ranks are each other's neighbours (the wrap columns / rows travel as ordinary segments); self_wrap: amt_cyclic_axes of
+    // the directions with ONE rank, refreshed by amt_cyclic_kernel on the domain's stream in front of every sweep.
+    bool wrap_x = false, wrap_y = false;
+    int self_wrap = 0;
     int skew_us = 0;                                        // test hook: the neighbours' rows arrive this late
     unsigned long long packs = 0;                           // exchanges begun (what AMT_TEST_FAULT skip_pack / skip_unpack count)
     // packed columns: what goes to the left / right neighbour, what came from the right / left one
@@ -65,6 +70,21 @@ __global__ __launch_bounds__(256) void amt_grid_columns(AmtColumnJobs<W> jobs)
     }
 }
 
+// First / last column and row a patch sends and the halo cells it receives into.  Without a cyclic flag: its, ite, jts, jte as
+// ever.  With one, the compute window's edges (amt_compute_window) instead: the last patch of a periodic direction may end at
+// ide-1 or at ide (jde-1 or jde), and what its neighbour across the domain edge reads is column ide-1 / row jde-1, what it
+// receives goes to column ide / row jde.  Interior patches' windows are their tiles (the flags' preconditions rule clipping out).
+struct EdgeCells { int ilo, ihi, jlo, jhi; };
+EdgeCells edge_cells(const amt_grid *g)
+{
+    const amt_domain *d = g->dom;
+    EdgeCells e{d->its, d->ite, d->jts, d->jte};
+    const AmtWindow w = amt_window(d->periodic_x, d->specified, d->nested, d->ids, d->ide, d->jds, d->jde, d->its, d->ite, d->jts, d->jte, d->kts, d->kte);
+    if (g->wrap_x || (g->self_wrap & AMT_CYCLIC_X)) { e.ilo = w.i_start; e.ihi = w.i_end; }
+    if (g->wrap_y || (g->self_wrap & AMT_CYCLIC_Y)) { e.jlo = w.j_start; e.jhi = w.j_end; }
+    return e;
+}
+
 struct ColumnPlan {
     size_t rows3, rows2, es;
     size_t bytes_from_right() const { return (3 * rows3 + 2 * rows2) * es; }      // u, u_1, t_1, muu, msfuy
@@ -91,7 +111,8 @@ int grid_columns(amt_grid *g, hipStream_t stream, bool scatter)
         jobs.count[q] = (long)(amt_field_rank(field) == 3 ? cp.rows3 : cp.rows2);
         jobs.packed[q] = static_cast<W *>(packed) + offset_elems;
     };
-    const long c_first = d->its - d->ims, c_last = d->ite - d->ims;
+    const EdgeCells ec = edge_cells(g);
+    const long c_first = ec.ilo - d->ims, c_last = ec.ihi - d->ims;
     const int side_a = scatter ? g->right : g->left;      // gather: what the LEFT neighbour needs; scatter: what came from the RIGHT
     const int side_b = scatter ? g->left : g->right;
     if (side_a >= 0) {
@@ -157,7 +178,8 @@ template <typename T>
 int grid_edges(amt_grid *g, hipStream_t edge_stream, bool lo, bool hi, bool lf, bool rt, bool unclipped, int in_jlo, int in_jhi)
 {
     amt_domain *d = g->dom;
-    const int ilo = d->its, ihi = d->ite, jlo = d->jts, jhi = d->jte;
+    const EdgeCells ec = edge_cells(g);
+    const int ilo = ec.ilo, ihi = ec.ihi, jlo = ec.jlo, jhi = ec.jhi;
     int rc = AMT_OK;
     // The boundary columns are independent of the rows and of each other: they go to streams of their own (three small
     // launches, the chip has room for all of them at once) behind the event "halos are in", and join the edge stream.
@@ -192,7 +214,8 @@ template <typename T>
 int grid_step_t(amt_grid *g, int n_sweeps)
 {
     amt_domain *d = g->dom;
-    const int ilo = d->its, ihi = d->ite, jlo = d->jts, jhi = d->jte;
+    const EdgeCells ec = edge_cells(g);
+    const int ilo = ec.ilo, ihi = ec.ihi, jlo = ec.jlo, jhi = ec.jhi;
     const bool lo = g->below >= 0, hi = g->above >= 0, lf = g->left >= 0, rt = g->right >= 0;
     // the rows the routine really updates in this patch (module_small_step_em.f90:91-106): with specified / nested boundaries
     // the first / last row of an outermost patch is clipped away.  Every tile below is clipped on its own by the same rule;
@@ -230,6 +253,13 @@ int grid_step_t(amt_grid *g, int n_sweeps)
         // that sweep's halo rows were not valid, so nothing is built on top of it -- the step fails here, not only in *_sync
         int rc = amt_exchange_check(g->xchg);
         if (rc) return rc;
+        // a cyclic direction with ONE rank: the patch is its own neighbour there, no transport -- the refresh kernel on the
+        // domain's stream in front of everything else of the sweep (the inputs are final here); that direction adds no
+        // boundary columns or rows to the edge launches
+        if (g->self_wrap) {
+            rc = amt_cyclic_refresh_domain("amt_grid_step", d, g->self_wrap, 1);
+            if (rc) return rc;
+        }
         if (none) {                                                        // a world of one: the plain launch
             rc = grid_tile<T>(g, d->stream, ilo, ihi, jlo, jhi);
             if (rc) return rc;
@@ -321,13 +351,33 @@ int grid_setup(amt_grid *g, amt_domain *dom, int ri, int rj, int pi, int pj, con
     if (comm_needed && !unique_id) return amt_fail(AMT_ERR_INVALID_ARG, "a communicator needs the unique id");
     g->dom = dom; g->ri = ri; g->rj = rj; g->pi = pi; g->pj = pj; g->rank = rank; g->world = world;
     g->overlap = !(flags & AMT_SLAB_NO_OVERLAP);
-    g->left = loop_i ? rank : ri > 0 ? rank - 1 : -1;
-    g->right = loop_i ? rank : ri < pi - 1 ? rank + 1 : -1;
-    g->below = loop_j ? rank : rj > 0 ? rank - pi : -1;
-    g->above = loop_j ? rank : rj < pj - 1 ? rank + pi : -1;
-    if ((g->below >= 0 || g->above >= 0) && (dom->jts - 1 < dom->jms || dom->jte + 1 > dom->jme))
+    const bool cyc_x = (flags & AMT_SLAB_CYCLIC_X) != 0, cyc_y = (flags & AMT_SLAB_CYCLIC_Y) != 0;
+    if ((cyc_x || cyc_y) && (loop_i || loop_j || (flags & AMT_SLAB_LOOPBACK)))
+        return amt_fail(AMT_ERR_INVALID_ARG, "AMT_SLAB_LOOPBACK cannot be combined with AMT_SLAB_CYCLIC_X / AMT_SLAB_CYCLIC_Y");
+    if (cyc_x && !dom->periodic_x && (dom->specified || dom->nested))
+        return amt_fail(AMT_ERR_PRECONDITION, "AMT_SLAB_CYCLIC_X needs an unclipped i window: periodic_x, or neither specified nor nested");
+    if (cyc_y && (dom->specified || dom->nested))
+        return amt_fail(AMT_ERR_PRECONDITION, "AMT_SLAB_CYCLIC_Y needs an unclipped j window: neither specified nor nested");
+    // Torus: with several ranks in a cyclic direction the edge ranks are each other's neighbours.  With exactly TWO, both
+    // neighbours are the same peer and there are two sets of segments per pair; the engine pairs the k-th segment sent to a
+    // peer with the k-th received from it, and the lists below keep that order: towards below / left first, then towards
+    // above / right, on the sending side; from above / right first, then from below / left, on the receiving side (what I
+    // send "below" is what my peer receives "from above").
+    g->wrap_x = cyc_x && pi > 1;
+    g->wrap_y = cyc_y && pj > 1;
+    g->self_wrap = (cyc_x && pi == 1 ? AMT_CYCLIC_X : 0) | (cyc_y && pj == 1 ? AMT_CYCLIC_Y : 0);
+    g->left = loop_i ? rank : ri > 0 ? rank - 1 : g->wrap_x ? rank + (pi - 1) : -1;
+    g->right = loop_i ? rank : ri < pi - 1 ? rank + 1 : g->wrap_x ? rank - (pi - 1) : -1;
+    g->below = loop_j ? rank : rj > 0 ? rank - pi : g->wrap_y ? rank + pi * (pj - 1) : -1;
+    g->above = loop_j ? rank : rj < pj - 1 ? rank + pi : g->wrap_y ? rank - pi * (pj - 1) : -1;
+    if (g->self_wrap) {
+        const int rc = amt_cyclic_check_domain("amt_grid_create", dom, g->self_wrap, 1);
+        if (rc) return rc;
+    }
+    const EdgeCells ec = edge_cells(g);
+    if ((g->below >= 0 || g->above >= 0) && (ec.jlo - 1 < dom->jms || ec.jhi + 1 > dom->jme))
         return amt_fail(AMT_ERR_PRECONDITION, "a patch holds one halo row below jts and above jte");
-    if ((g->left >= 0 || g->right >= 0) && (dom->its - 1 < dom->ims || dom->ite + 1 > dom->ime))
+    if ((g->left >= 0 || g->right >= 0) && (ec.ilo - 1 < dom->ims || ec.ihi + 1 > dom->ime))
         return amt_fail(AMT_ERR_PRECONDITION, "a patch holds one halo column left of its and right of ite");
     int transport = (flags & AMT_SLAB_TRANSPORT_IPC) ? AMT_XCHG_IPC : AMT_XCHG_RCCL;
     if (const char *e = getenv("AMT_SLAB_TRANSPORT")) {                  // hosts that cannot pass the flag (the Fortran drivers)
@@ -363,12 +413,12 @@ int grid_setup(amt_grid *g, amt_domain *dom, int ri, int rj, int pi, int pj, con
         return AmtSeg{static_cast<char *>(dom->field[f]) + (size_t)(j - dom->jms) * count * dom->dtype_bytes, count * dom->dtype_bytes, peer};
     };
     std::vector<AmtSeg> sends, recvs;
-    if (g->below >= 0) for (int f : kRowsFromAbove) sends.push_back(row(f, dom->jts, g->below));
-    if (g->above >= 0) for (int f : kRowsFromBelow) sends.push_back(row(f, dom->jte, g->above));
+    if (g->below >= 0) for (int f : kRowsFromAbove) sends.push_back(row(f, ec.jlo, g->below));
+    if (g->above >= 0) for (int f : kRowsFromBelow) sends.push_back(row(f, ec.jhi, g->above));
     if (g->left >= 0) sends.push_back(AmtSeg{g->to_left, cp.bytes_from_right(), g->left});
     if (g->right >= 0) sends.push_back(AmtSeg{g->to_right, cp.bytes_from_left(), g->right});
-    if (g->above >= 0) for (int f : kRowsFromAbove) recvs.push_back(row(f, dom->jte + 1, g->above));
-    if (g->below >= 0) for (int f : kRowsFromBelow) recvs.push_back(row(f, dom->jts - 1, g->below));
+    if (g->above >= 0) for (int f : kRowsFromAbove) recvs.push_back(row(f, ec.jhi + 1, g->above));
+    if (g->below >= 0) for (int f : kRowsFromBelow) recvs.push_back(row(f, ec.jlo - 1, g->below));
     if (g->right >= 0) recvs.push_back(AmtSeg{g->from_right, cp.bytes_from_right(), g->right});
     if (g->left >= 0) recvs.push_back(AmtSeg{g->from_left, cp.bytes_from_left(), g->left});
     return amt_exchange_create(&g->xchg, transport, rank, world, unique_id, dom->device, sends.data(), (int)sends.size(),
@@ -380,7 +430,8 @@ int grid_exchange_only(amt_grid *g)
     DeviceScope scope(g->dom->device);
     AMT_HIP(hipEventRecord(g->inputs_final, g->dom->stream));
     AMT_HIP(hipStreamWaitEvent(g->comm_stream, g->inputs_final, 0));
-    int rc = grid_pack(g, g->comm_stream);
+    int rc = g->self_wrap ? amt_cyclic_refresh_domain("amt_grid_exchange", g->dom, g->self_wrap, 1) : AMT_OK;   // on the domain's stream
+    if (rc == AMT_OK) rc = grid_pack(g, g->comm_stream);
     if (rc == AMT_OK) rc = amt_exchange_enqueue(g->xchg, g->comm_stream, true);
     if (rc == AMT_OK) rc = grid_unpack(g, g->comm_stream);
     if (rc == AMT_OK) rc = amt_exchange_enqueue_release(g->xchg, g->comm_stream);

@@ -136,6 +136,7 @@ struct amt_domain {
     void *field[AMT_F_COUNT] = {};
     bool owns_fields = true;      // false: the arrays belong to the caller (amt_domain_wrap)
     bool owns_stream = true;      // false: the stream belongs to the caller
+    int cyclic = 0;               // amt_cyclic_axes refreshed in front of every sweep (amt_domain_set_cyclic); 0 = off
     int placement_tries = 0;      // allocations of the state that were timed (amt_domain_create / amt_domain_tune_placement)
     float placement_ms[16] = {};  // sweep time on each (0: not tried)
     size_t count(int f) const
@@ -164,3 +165,10 @@ inline void amt_domain_args(amt_domain *d, AmtArgs<T> &a)
     a.ims = d->ims; a.ime = d->ime; a.jms = d->jms; a.jme = d->jme; a.kms = d->kms; a.kme = d->kme;
     a.its = d->its; a.ite = d->ite; a.jts = d->jts; a.jte = d->jte; a.kts = d->kts; a.kte = d->kte;
 }
+
+// ---------------------------------------------------------------------------
+// cyclic lateral boundaries (amt_cyclic.hip): one refresh of `members` member-stacked patches of the domain's shape on the
+// domain's stream, and the argument / precondition checks alone (host arithmetic)
+// ---------------------------------------------------------------------------
+int amt_cyclic_refresh_domain(const char *who, amt_domain *d, int axes, int members);
+int amt_cyclic_check_domain(const char *who, const amt_domain *d, int axes, int members);

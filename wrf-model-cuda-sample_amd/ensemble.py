@@ -181,6 +181,18 @@ class Ensemble:
         _lib.check(self.L.amt_ensemble_step_timed(self.handle, int(n_sweeps), ctypes.byref(ms)))
         return float(ms.value)
 
+    def set_cyclic(self, axes: int) -> None:
+        """``amt_ensemble_set_cyclic``: CYCLIC_X | CYCLIC_Y of api.py; every sweep of ``step`` / ``step_timed`` is then preceded
+        by one refresh launch over all members.  0 = off."""
+        _lib.check(self.L.amt_ensemble_set_cyclic(self.handle, int(axes)))
+
+    def cyclic(self) -> int:
+        return int(self.L.amt_ensemble_cyclic(self.handle))
+
+    def cyclic_fill(self, axes: int) -> None:
+        """``amt_ensemble_cyclic_fill``: one refresh of every member now, asynchronous on the handle's stream."""
+        _lib.check(self.L.amt_ensemble_cyclic_fill(self.handle, int(axes)))
+
     def sync(self) -> None:
         _lib.check(self.L.amt_ensemble_sync(self.handle))
 

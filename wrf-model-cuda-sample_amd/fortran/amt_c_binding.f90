@@ -8,7 +8,8 @@ MODULE amt_c_binding
 
    integer(c_int), parameter :: AMT_OK = 0
    ! enum amt_slab_flags (amt_slab_create / amt_grid_create)
-   integer(c_int), parameter :: AMT_SLAB_NO_OVERLAP = 1, AMT_SLAB_LOOPBACK = 2, AMT_SLAB_TRANSPORT_IPC = 4
+   integer(c_int), parameter :: AMT_SLAB_NO_OVERLAP = 1, AMT_SLAB_LOOPBACK = 2, AMT_SLAB_TRANSPORT_IPC = 4,  &
+                                AMT_SLAB_CYCLIC_X = 8, AMT_SLAB_CYCLIC_Y = 16
 
    interface
       ! (1) one-shot host drop-ins
@@ -501,6 +502,70 @@ MODULE amt_c_binding
          integer(c_int), value :: members, nj, cus, wbytes, hl
          integer(c_int) :: rows
       end function
+      ! cyclic (periodic) lateral boundaries (header section 9): axes = AMT_CYCLIC_X, AMT_CYCLIC_Y or their sum.  Pointer level, for
+      ! hosts that keep their own device arrays (members = 1 for a single patch); asynchronous on hip_stream
+      function amt_cyclic_fill_device_f32(hip_stream, axes, members, u, u_1, v, v_1, t_1, muu, muv, msfuy, msfvx_inv,   &
+                                          periodic_x, specified, nested,                                                &
+                                          ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,                        &
+                                          its, ite, jts, jte, kts, kte) bind(C, name="amt_cyclic_fill_device_f32") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: hip_stream
+         integer(c_int), value :: axes, members
+         type(c_ptr), value :: u, u_1, v, v_1, t_1, muu, muv, msfuy, msfvx_inv      ! device pointers
+         integer(c_int), value :: periodic_x, specified, nested
+         integer(c_int), value :: ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme
+         integer(c_int), value :: its, ite, jts, jte, kts, kte
+         integer(c_int) :: rc
+      end function
+      function amt_cyclic_fill_device_f64(hip_stream, axes, members, u, u_1, v, v_1, t_1, muu, muv, msfuy, msfvx_inv,   &
+                                          periodic_x, specified, nested,                                                &
+                                          ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,                        &
+                                          its, ite, jts, jte, kts, kte) bind(C, name="amt_cyclic_fill_device_f64") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: hip_stream
+         integer(c_int), value :: axes, members
+         type(c_ptr), value :: u, u_1, v, v_1, t_1, muu, muv, msfuy, msfvx_inv      ! device pointers
+         integer(c_int), value :: periodic_x, specified, nested
+         integer(c_int), value :: ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme
+         integer(c_int), value :: its, ite, jts, jte, kts, kte
+         integer(c_int) :: rc
+      end function
+      ! one refresh now, on the handle's stream
+      function amt_domain_cyclic_fill(handle, axes) bind(C, name="amt_domain_cyclic_fill") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: axes
+         integer(c_int) :: rc
+      end function
+      ! 0 = off; otherwise every sweep of amt_domain_step / amt_domain_step_timed is preceded by a refresh
+      function amt_domain_set_cyclic(handle, axes) bind(C, name="amt_domain_set_cyclic") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: axes
+         integer(c_int) :: rc
+      end function
+      function amt_domain_cyclic(handle) bind(C, name="amt_domain_cyclic") result(axes)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int) :: axes
+      end function
+      function amt_ensemble_cyclic_fill(handle, axes) bind(C, name="amt_ensemble_cyclic_fill") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: axes
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_set_cyclic(handle, axes) bind(C, name="amt_ensemble_set_cyclic") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: axes
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_cyclic(handle) bind(C, name="amt_ensemble_cyclic") result(axes)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int) :: axes
+      end function
    end interface
 
    ! enum amt_field (include/amt_synth.h): the Fortran argument order
@@ -515,6 +580,8 @@ MODULE amt_c_binding
       ior(ishft(1_c_int64_t, 11), ior(ishft(1_c_int64_t, 22), ishft(1_c_int64_t, 23)))))
    ! enum amt_sides (amt_domain_poison_halos)
    integer(c_int), parameter :: AMT_SIDE_BELOW = 1, AMT_SIDE_ABOVE = 2, AMT_SIDE_LEFT = 4, AMT_SIDE_RIGHT = 8
+   ! enum amt_cyclic_axes (amt_cyclic_fill_device_*, amt_domain_set_cyclic, amt_ensemble_set_cyclic)
+   integer(c_int), parameter :: AMT_CYCLIC_X = 1, AMT_CYCLIC_Y = 2
 
 CONTAINS
 

@@ -133,6 +133,14 @@ SYMBOLS = {
     "amt_ensemble_field_ptr": (_P, [_P, _I]),
     "amt_ensemble_stream": (_P, [_P]),
     "amt_march_rows_for_members": (_I, [ctypes.c_long, _I, _I, _I, ctypes.c_long, _I, _I]),
+    "amt_cyclic_fill_device_f32": (_I, [_P, _I, _I] + [_P] * 9 + [_I] * (3 + 17)),
+    "amt_cyclic_fill_device_f64": (_I, [_P, _I, _I] + [_P] * 9 + [_I] * (3 + 17)),
+    "amt_domain_cyclic_fill": (_I, [_P, _I]),
+    "amt_domain_set_cyclic": (_I, [_P, _I]),
+    "amt_domain_cyclic": (_I, [_P]),
+    "amt_ensemble_cyclic_fill": (_I, [_P, _I]),
+    "amt_ensemble_set_cyclic": (_I, [_P, _I]),
+    "amt_ensemble_cyclic": (_I, [_P]),
     "amt_march_force_shape": (_I, [_I] * 7),
     "amt_march_rows_for": (_I, [ctypes.c_long, _I, _I, ctypes.c_long, _I, _I]),
     "amt_march_set_xchunk": (_I, [_I]),

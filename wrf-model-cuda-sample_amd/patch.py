@@ -38,6 +38,74 @@ def _fault(step: str, occurrence: int) -> bool:
     return bool(spec) and spec == f"{step}@{occurrence}"
 
 
+CYCLIC_X_FLAG, CYCLIC_Y_FLAG = 8, 16            # AMT_SLAB_CYCLIC_X, AMT_SLAB_CYCLIC_Y of enum amt_slab_flags
+
+
+def cyclic_sides(ri: int, rj: int, pi: int, pj: int, cyclic=(False, False)) -> int:
+    """The sides of patch (ri, rj) of pi x pj whose halo is delivered every sweep: by a neighbour, or -- in a cyclic
+    direction -- by the rank across the domain edge or by the patch itself (one rank in that direction)."""
+    sides = _S.neighbour_sides(ri, rj, pi, pj)
+    if cyclic[0]:
+        sides |= _S.SIDE_LEFT | _S.SIDE_RIGHT
+    if cyclic[1]:
+        sides |= _S.SIDE_BELOW | _S.SIDE_ABOVE
+    return sides
+
+
+def _edge_cells(b):
+    """Memory indices (c_first, c_last, r_first, r_last) of the compute window's edge columns and rows: what a patch sends
+    across a cyclic domain edge, and next to which it receives (a last patch may end at ide-1 or at ide)."""
+    return (b.its - b.ims, min(b.ite, b.ide - 1) - b.ims, b.jts - b.jms, min(b.jte, b.jde - 1) - b.jms)
+
+
+def _self_wrap(patch: Patch, x: bool, y: bool) -> None:
+    """A cyclic direction with ONE rank: the patch is its own neighbour there.  Column i_end+1 <-
+    i_start of HALO_FROM_RIGHT and i_start-1 <- i_end of t_1 over the window's rows; row j_end+1 <- j_start of HALO_FROM_ABOVE
+    and j_start-1 <- j_end of t_1 over the window's columns.  Torch slicing, for the CPU (gloo) tests and bring-up."""
+    a = patch.arrays
+    c0, c1, r0, r1 = _edge_cells(patch.bounds)
+    if x:
+        for name in _S.HALO_FROM_RIGHT:
+            a[name][r0:r1 + 1, ..., c1 + 1] = a[name][r0:r1 + 1, ..., c0]
+        a["t_1"][r0:r1 + 1, :, c0 - 1] = a["t_1"][r0:r1 + 1, :, c1]
+    if y:
+        for name in HALO_FROM_ABOVE:
+            a[name][r1 + 1, ..., c0:c1 + 1] = a[name][r0, ..., c0:c1 + 1]
+        a["t_1"][r0 - 1, :, c0:c1 + 1] = a["t_1"][r1, :, c0:c1 + 1]
+
+
+def exchange_plan(ri: int, rj: int, pi: int, pj: int, cyclic=(False, False)):
+    """Neighbours and the ORDER of the segments of one exchange of patch (ri, rj) of pi x pj, as amt_grid_create builds them
+    (csrc/amt_grid.hip): (left, right, below, above, sends, recvs), a neighbour None where there is none, sends / recvs lists
+    of (peer, what).  Per pair of ranks the k-th send to a peer is the k-th receive from it on the other side -- also when both
+    neighbours of a direction are the SAME peer (two ranks in a cyclic direction): towards below / left first on the sending
+    side, from above / right first on the receiving side."""
+    rank = rj * pi + ri
+    wx, wy = bool(cyclic[0]) and pi > 1, bool(cyclic[1]) and pj > 1
+    left = rank - 1 if ri > 0 else rank + (pi - 1) if wx else None
+    right = rank + 1 if ri < pi - 1 else rank - (pi - 1) if wx else None
+    below = rank - pi if rj > 0 else rank + pi * (pj - 1) if wy else None
+    above = rank + pi if rj < pj - 1 else rank - pi * (pj - 1) if wy else None
+    sends, recvs = [], []
+    if below is not None:
+        sends += [(below, f"row_first:{n}") for n in HALO_FROM_ABOVE]
+    if above is not None:
+        sends += [(above, f"row_last:{n}") for n in HALO_FROM_BELOW]
+    if left is not None:
+        sends.append((left, "cols_first"))
+    if right is not None:
+        sends.append((right, "cols_last"))
+    if above is not None:
+        recvs += [(above, f"row_first:{n}") for n in HALO_FROM_ABOVE]
+    if below is not None:
+        recvs += [(below, f"row_last:{n}") for n in HALO_FROM_BELOW]
+    if right is not None:
+        recvs.append((right, "cols_first"))
+    if left is not None:
+        recvs.append((left, "cols_last"))
+    return left, right, below, above, sends, recvs
+
+
 class SlabStepper:
     """Runs advance_mu_t sweeps on one j-slab of a domain split over ``world`` ranks.
 
@@ -50,8 +118,11 @@ class SlabStepper:
 
     def __init__(self, patch: Patch, rank: int, world: int, compute: Callable, *,
                  group=None, overlap: bool = True, variant: int = 0, transport: Optional[Callable] = None,
-                 stage_through_host: bool = False):
+                 stage_through_host: bool = False, cyclic=(False, False)):
         self.patch, self.rank, self.world = patch, rank, world
+        # cyclic = (x, y): the domain is periodic in that direction.  x: a slab holds the whole period:
+        # self wrap in front of every sweep.  y: slab 0 and slab world-1 are each other's neighbours (world == 1: self wrap).
+        self.cyclic = (bool(cyclic[0]), bool(cyclic[1]))
         self.compute, self.group, self.overlap, self.variant = compute, group, overlap, variant
         # transport(stepper): replaces the torch.distributed exchange (tests run several slabs of
         # one domain in ONE process on one GPU and copy the halo rows device-to-device)
@@ -63,6 +134,9 @@ class SlabStepper:
         self.stage_through_host = stage_through_host
         self.below: Optional[int] = rank - 1 if rank > 0 else None
         self.above: Optional[int] = rank + 1 if rank < world - 1 else None
+        if self.cyclic[1] and world > 1:
+            self.below = self.below if self.below is not None else world - 1
+            self.above = self.above if self.above is not None else 0
         any_arr = patch.arrays["t_1"]
         self.on_gpu = bool(getattr(any_arr, "is_cuda", False))
         self.main_stream = self.comm_stream = None
@@ -82,6 +156,9 @@ class SlabStepper:
         a = self.patch.arrays
         jdim = self.patch.bounds.jdim
         first_owned, last_owned, halo_lo, halo_hi = 1, jdim - 2, 0, jdim - 1
+        if self.cyclic[1]:                                 # the window's edge rows: a last slab may end at jde-1 or at jde
+            _c0, _c1, first_owned, last_owned = _edge_cells(self.patch.bounds)
+            halo_lo, halo_hi = first_owned - 1, last_owned + 1
         ops = []
         # order per peer pair is fixed (NCCL/RCCL matches send/recv by order, gloo by tag)
         if self.below is not None:
@@ -158,6 +235,10 @@ class SlabStepper:
     def step(self):
         b = self.patch.bounds
         jlo, jhi = b.jts, b.jte
+        if self.cyclic[1]:
+            jhi = min(jhi, b.jde - 1)
+        if self.cyclic[0] or (self.cyclic[1] and self.world == 1):
+            _self_wrap(self.patch, self.cyclic[0], self.cyclic[1] and self.world == 1)      # on the current stream: inputs are final
         if self.world == 1 or (self.below is None and self.above is None):
             self._tile(jlo, jhi, self.main_stream)
             return
@@ -203,8 +284,9 @@ class GridStepper:
 
     def __init__(self, patch: Patch, ri: int, rj: int, pi: int, pj: int, compute: Callable, *,
                  group=None, variant: int = 0, stage_through_host: bool = False,
-                 native: Optional[str] = None, unique_id: Optional[bytes] = None, overlap: bool = True):
+                 native: Optional[str] = None, unique_id: Optional[bytes] = None, overlap: bool = True, cyclic=(False, False)):
         self.patch, self.ri, self.rj, self.pi, self.pj = patch, ri, rj, pi, pj
+        self.cyclic = (bool(cyclic[0]), bool(cyclic[1]))      # the torus topology of amt_grid_create (exchange_plan)
         self.compute, self.group, self.variant = compute, group, variant
         self.stage_through_host = stage_through_host
         # native="rccl" | "ipc": a device patch is stepped by the C++ runtime (amt_grid_*: HIP pack / unpack kernels, one
@@ -212,14 +294,19 @@ class GridStepper:
         # over gloo in the tests; device tensors staged through the host for bring-up)
         self._native = None
         if native is not None:
-            self._native = NativeGridStepper(patch, ri, rj, pi, pj, unique_id, overlap=overlap, variant=variant, transport=native)
-        rank = lambda i, j: j * pi + i
-        self.left = rank(ri - 1, rj) if ri > 0 else None
-        self.right = rank(ri + 1, rj) if ri < pi - 1 else None
-        self.below = rank(ri, rj - 1) if rj > 0 else None
-        self.above = rank(ri, rj + 1) if rj < pj - 1 else None
+            self._native = NativeGridStepper(patch, ri, rj, pi, pj, unique_id, overlap=overlap, variant=variant, transport=native,
+                                             cyclic=self.cyclic)
+        self.left, self.right, self.below, self.above, _sends, _recvs = exchange_plan(ri, rj, pi, pj, self.cyclic)
+        self._self = (self.cyclic[0] and pi == 1, self.cyclic[1] and pj == 1)
         b = patch.bounds
         self.c_first, self.c_last = b.its - b.ims, b.ite - b.ims          # owned columns (memory index)
+        self.r_first, self.r_last = 1, b.jdim - 2
+        if any(self.cyclic):                                                # the window's edges (a last patch may end at ide / jde)
+            c0, c1, r0, r1 = _edge_cells(b)
+            if self.cyclic[0]:
+                self.c_first, self.c_last = c0, c1
+            if self.cyclic[1]:
+                self.r_first, self.r_last = r0, r1
         self.c_halo_l, self.c_halo_r = self.c_first - 1, self.c_last + 1
         self.on_gpu = bool(getattr(patch.arrays["t_1"], "is_cuda", False))
         self._call = None
@@ -234,9 +321,10 @@ class GridStepper:
         self._exchanges = getattr(self, "_exchanges", 0) + 1
         if _fault("skip_exchange", self._exchanges):
             return
+        if any(self._self):
+            _self_wrap(self.patch, *self._self)
         dist = _dist()
         a = self.patch.arrays
-        jdim = self.patch.bounds.jdim
         ops, unpack = [], []
         host = self.stage_through_host and self.on_gpu
 
@@ -254,12 +342,12 @@ class GridStepper:
 
         if self.below is not None:
             for n, name in enumerate(HALO_FROM_ABOVE):
-                send(a[name][1], self.below, 10 + n)
-            recv(a["t_1"][0], self.below, 20, False)
+                send(a[name][self.r_first], self.below, 10 + n)
+            recv(a["t_1"][self.r_first - 1], self.below, 20, False)
         if self.above is not None:
             for n, name in enumerate(HALO_FROM_ABOVE):
-                recv(a[name][jdim - 1], self.above, 10 + n, False)
-            send(a["t_1"][jdim - 2], self.above, 20)
+                recv(a[name][self.r_last + 1], self.above, 10 + n, False)
+            send(a["t_1"][self.r_last], self.above, 20)
         if self.left is not None:
             for n, name in enumerate(HALO_FROM_RIGHT):     # my first column is their column ihi+1
                 send(self._col(name, self.c_first), self.left, 30 + n)
@@ -324,7 +412,8 @@ class NativeSlabStepper:
     NO_OVERLAP, LOOPBACK, TRANSPORT_IPC = 1, 2, 4          # enum amt_slab_flags
 
     def __init__(self, patch: Patch, rank: int, world: int, unique_id: Optional[bytes] = None, *,
-                 stream=None, overlap: bool = True, variant: int = 0, loopback: bool = False, transport: str = "rccl"):
+                 stream=None, overlap: bool = True, variant: int = 0, loopback: bool = False, transport: str = "rccl",
+                 cyclic=(False, False)):
         import ctypes
         import torch
         from . import lib as _lib
@@ -332,9 +421,10 @@ class NativeSlabStepper:
         self._lib, self._ct = _lib, ctypes
         self.L = L = _lib.load_library()
         self.patch, self.rank, self.world = patch, rank, world
+        self.cyclic = (bool(cyclic[0]), bool(cyclic[1]))      # AMT_SLAB_CYCLIC_X / _Y: x is a self wrap of the slab, y a torus
         self.below: Optional[int] = rank - 1 if rank > 0 else None
         self.above: Optional[int] = rank + 1 if rank < world - 1 else None
-        self._halo_sides = (_S.SIDE_BELOW | _S.SIDE_ABOVE) if loopback else _S.neighbour_sides(0, rank, 1, world)
+        self._halo_sides = (_S.SIDE_BELOW | _S.SIDE_ABOVE) if loopback else cyclic_sides(0, rank, 1, world, self.cyclic)
         t0 = patch.arrays["t_1"]
         if not t0.is_cuda:
             raise TypeError("NativeSlabStepper needs a device patch (there is no CPU path)")
@@ -356,7 +446,8 @@ class NativeSlabStepper:
                 if transport not in ("rccl", "ipc"):
                     raise ValueError("transport is 'rccl' or 'ipc'")
                 flags = ((0 if overlap else self.NO_OVERLAP) | (self.LOOPBACK if loopback else 0)
-                         | (self.TRANSPORT_IPC if transport == "ipc" else 0))
+                         | (self.TRANSPORT_IPC if transport == "ipc" else 0)
+                         | (CYCLIC_X_FLAG if self.cyclic[0] else 0) | (CYCLIC_Y_FLAG if self.cyclic[1] else 0))
                 uid = None
                 if unique_id is not None:
                     uid = (ctypes.c_char * 128).from_buffer_copy(bytes(unique_id))
@@ -445,7 +536,8 @@ class NativeGridStepper:
     NO_OVERLAP, LOOPBACK, TRANSPORT_IPC = 1, 2, 4          # enum amt_slab_flags
 
     def __init__(self, patch: Patch, ri: int, rj: int, pi: int, pj: int, unique_id: Optional[bytes] = None, *,
-                 stream=None, overlap: bool = True, variant: int = 0, loopback: bool = False, transport: str = "rccl"):
+                 stream=None, overlap: bool = True, variant: int = 0, loopback: bool = False, transport: str = "rccl",
+                 cyclic=(False, False)):
         import ctypes
         import torch
         from . import lib as _lib
@@ -453,7 +545,8 @@ class NativeGridStepper:
         self._lib, self._ct = _lib, ctypes
         self.L = L = _lib.load_library()
         self.patch, self.ri, self.rj, self.pi, self.pj = patch, ri, rj, pi, pj
-        self._halo_sides = 15 if loopback else _S.neighbour_sides(ri, rj, pi, pj)
+        self.cyclic = (bool(cyclic[0]), bool(cyclic[1]))      # AMT_SLAB_CYCLIC_X / _Y
+        self._halo_sides = 15 if loopback else cyclic_sides(ri, rj, pi, pj, self.cyclic)
         t0 = patch.arrays["t_1"]
         if not t0.is_cuda:
             raise TypeError("NativeGridStepper needs a device patch (there is no CPU path)")
@@ -475,7 +568,8 @@ class NativeGridStepper:
                 _lib.check(L.amt_domain_set_scalars(self._dom, patch.rdx, patch.rdy, patch.dts, patch.epssm))
                 _lib.check(L.amt_domain_set_variant(self._dom, int(variant)))
                 flags = ((0 if overlap else self.NO_OVERLAP) | (self.LOOPBACK if loopback else 0)
-                         | (self.TRANSPORT_IPC if transport == "ipc" else 0))
+                         | (self.TRANSPORT_IPC if transport == "ipc" else 0)
+                         | (CYCLIC_X_FLAG if self.cyclic[0] else 0) | (CYCLIC_Y_FLAG if self.cyclic[1] else 0))
                 uid = None
                 if unique_id is not None:
                     uid = (ctypes.c_char * 128).from_buffer_copy(bytes(unique_id))

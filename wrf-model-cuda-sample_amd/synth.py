@@ -206,6 +206,18 @@ class NativeDomain:
         n = int(self.L.amt_domain_placement(self.handle, ms, 16))
         return [round(float(ms[k]), 3) for k in range(n) if ms[k] > 0]
 
+    def set_cyclic(self, axes: int) -> None:
+        """``amt_domain_set_cyclic``: CYCLIC_X | CYCLIC_Y of api.py; every sweep of the handle's own stepping
+        (``amt_domain_step``) is then preceded by a refresh of the wrap cells.  0 = off."""
+        _lib.check(self.L.amt_domain_set_cyclic(self.handle, int(axes)))
+
+    def cyclic(self) -> int:
+        return int(self.L.amt_domain_cyclic(self.handle))
+
+    def cyclic_fill(self, axes: int) -> None:
+        """``amt_domain_cyclic_fill``: one refresh now, asynchronous on the handle's stream."""
+        _lib.check(self.L.amt_domain_cyclic_fill(self.handle, int(axes)))
+
     def view(self, field_id: int, shape, typestr: str):
         ptr = self.L.amt_domain_field_ptr(self.handle, field_id)
         if not ptr:
