@@ -61,7 +61,8 @@ typedef enum amt_status {
     AMT_ERR_INVALID_ARG = 3,   /* null pointer, bad dtype / field id / variant      */
     AMT_ERR_NO_DEVICE = 4,     /* no gfx950 device visible                          */
     AMT_ERR_ALLOC = 5,         /* device or host allocation failed                  */
-    AMT_ERR_COMM = 6           /* RCCL could not be loaded or a collective call failed */
+    AMT_ERR_COMM = 6,          /* RCCL could not be loaded or a collective call failed */
+    AMT_ERR_NONFINITE = 7      /* the non-finite guard of section (10) found a NaN or Inf in ww, t or mu */
 } amt_status;
 
 /* Kernel variants (amt_set_variant / `variant` arguments).  AMT_VARIANT_AUTO picks
@@ -657,6 +658,81 @@ int amt_domain_cyclic(const amt_domain *d);                        /* the axes s
 int amt_ensemble_cyclic_fill(amt_ensemble *e, int axes);
 int amt_ensemble_set_cyclic(amt_ensemble *e, int axes);
 int amt_ensemble_cyclic(const amt_ensemble *e);
+
+/* ------------------------------------------------------------------------
+ * (10) Looking at resident state without downloading it: statistics of a field, a bit comparison of two fields, and a guard
+ *      that watches ww, t and mu for NaN / Inf while the handle steps.  Each is ONE read of the field on the device.
+ *      BOX: Fortran-inclusive i0..i1, k0..k1, j0..j1 inside the memory extents ims:ime, kms:kme, jms:jme of a rank-3 field
+ *      (rank 2: the k arguments are ignored); with `members` > 1 the arrays are member-stacked as in (8) and every member gets
+ *      a record of its own over the same box.  Cells outside the box never influence a result (halo cells may hold NaN) and
+ *      nothing outside the array is read.  OFFSETS are element offsets from the MEMBER's base in the layout of (3).
+ *      DETERMINISM: a member's record is a function of that member's box contents and the box shape alone -- not of the
+ *      address, the stream, the run, or of what is stacked beside it (fixed partition, partials folded in index order, no
+ *      floating-point atomics): `sum` has the same bits every time.
+ *      Argument errors (a box outside the extents or empty, rank not 2 or 3, members < 1, a NULL pointer, a rank-1 field, an
+ *      unknown region) are AMT_ERR_INVALID_ARG and are reported before any device call; `out` is then untouched.
+ * ------------------------------------------------------------------------ */
+typedef struct amt_field_stats {
+    int64_t count;            /* elements in the box */
+    int64_t n_nan, n_inf;
+    int64_t first_nonfinite;  /* smallest element offset from the MEMBER's base of a NaN/Inf in the box, -1: none */
+    double  min, max, max_abs;/* over the finite elements; +inf, -inf, 0 when there is none */
+    double  sum;              /* of the finite elements, each converted to double exactly, added in double */
+} amt_field_stats;
+
+typedef struct amt_field_diff {
+    int64_t count;
+    int64_t n_diff;           /* elements whose BIT PATTERNS differ (-0.0 vs +0.0 differs; equal NaN payloads do not) */
+    int64_t first_diff;       /* smallest offset from the member's base, -1: none */
+    double  max_abs_diff;     /* max |a-b| over pairs with both finite, in double; 0 when there is none */
+} amt_field_diff;
+
+typedef struct amt_guard_report {
+    int64_t sweeps_checked;   /* sweeps after which the guard looked, since it was armed */
+    int64_t sweep;            /* sweep of the first finding, 1-based since arming; 0 = none (the fields below are then 0) */
+    int32_t field;            /* enum amt_field: AMT_F_WW, AMT_F_T or AMT_F_MU */
+    int32_t member;           /* 0 for a domain */
+    int64_t offset;           /* of the first non-finite element, from the member's base */
+    int64_t n_nonfinite;      /* NaN + Inf of that field and member at that sweep */
+} amt_guard_report;
+
+/* pointer level, beside amt_advance_mu_t_device_*: enqueued on hip_stream (NULL = the default stream), waits for that stream
+ * and fills out[0 .. members-1] in HOST memory.  The workspace is kept per calling host thread. */
+int amt_stats_device_f32(void *hip_stream, const float *a, int rank, int members,
+                         int ims, int ime, int jms, int jme, int kms, int kme,
+                         int i0, int i1, int k0, int k1, int j0, int j1, amt_field_stats *out);
+int amt_stats_device_f64(void *hip_stream, const double *a, int rank, int members,
+                         int ims, int ime, int jms, int jme, int kms, int kme,
+                         int i0, int i1, int k0, int k1, int j0, int j1, amt_field_stats *out);
+int amt_compare_device_f32(void *hip_stream, const float *a, const float *b, int rank, int members,
+                           int ims, int ime, int jms, int jme, int kms, int kme,
+                           int i0, int i1, int k0, int k1, int j0, int j1, amt_field_diff *out);
+int amt_compare_device_f64(void *hip_stream, const double *a, const double *b, int rank, int members,
+                           int ims, int ime, int jms, int jme, int kms, int kme,
+                           int i0, int i1, int k0, int k1, int j0, int j1, amt_field_diff *out);
+
+/* handle level.  AMT_REGION_WINDOW: i_start..i_end, j_start..j_end of amt_compute_window, levels k_start..k_end for a rank-3
+ * field; AMT_REGION_MEMORY: the whole extents.  Synchronous: the work runs on the handle's stream behind whatever is enqueued
+ * there.  The compare calls take two handles of the same dtype, bounds and member count on one device; the work is enqueued
+ * on a's stream after b's stream has been waited for.  An ensemble fills `members` records. */
+enum amt_region { AMT_REGION_WINDOW = 0, AMT_REGION_MEMORY = 1 };
+int amt_domain_field_stats(amt_domain *d, int field, int region, amt_field_stats *out);
+int amt_ensemble_field_stats(amt_ensemble *e, int field, int region, amt_field_stats *out);
+int amt_domain_compare(amt_domain *a, amt_domain *b, int field, int region, amt_field_diff *out);
+int amt_ensemble_compare(amt_ensemble *a, amt_ensemble *b, int field, int region, amt_field_diff *out);
+
+/* Non-finite guard.  every = 0: off (the default; the step path enqueues exactly what it does without this section) and
+ * any finding is cleared.  every = n >= 1: armed, any finding cleared; after every n-th sweep enqueued by *_step /
+ * *_step_timed since arming, one statistics launch each for ww, t and mu over AMT_REGION_WINDOW runs on the handle's stream
+ * (wrapped handles: the caller's), with no host wait and no allocation.  The FIRST finding -- earliest checked sweep, then
+ * lowest member, then ww before t before mu, then smallest offset -- is sticky: the kernel writes it into a page-locked
+ * host record.  With a finding present *_sync and *_step_timed return AMT_ERR_NONFINITE; *_step returns it WITHOUT enqueuing
+ * anything when the finding is already visible at the call (it never waits); amt_last_error() names the sweep, the field,
+ * the member and (i,k,j).  *_guard_report waits for the stream and fills the record (all zero with the guard off). */
+int amt_domain_set_guard(amt_domain *d, int every);
+int amt_ensemble_set_guard(amt_ensemble *e, int every);
+int amt_domain_guard_report(amt_domain *d, amt_guard_report *out);
+int amt_ensemble_guard_report(amt_ensemble *e, amt_guard_report *out);
 
 #ifdef __cplusplus
 }

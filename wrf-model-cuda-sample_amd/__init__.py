@@ -11,6 +11,8 @@ Host-side mirror of the reference's interface for this one path:
 * ``wrfdump``            -- the reference drivers' big-endian per-variable dump format.
 * ``ensemble``           -- ``members`` same-shape patches advanced by one launch per sweep
   (``advance_mu_t_ensemble``, ``Ensemble``; member-stacked arrays).
+* ``diag``               -- statistics and bit comparison of torch device tensors on the device
+  (``field_stats``, ``compare``); the resident handles carry the same plus a non-finite guard.
 * ``patch``              -- resident device patch (torch-allocated arrays) and j-slab
   decomposition with the one-row input-halo exchange over torch.distributed (RCCL).
 
@@ -21,6 +23,7 @@ every compute entry point raises.
 """
 from .config import GridConfig  # noqa: F401
 from .lib import AmtError, load_library, library_path  # noqa: F401
+from .lib import FieldStats, FieldDiff, GuardReport, REGION_WINDOW, REGION_MEMORY  # noqa: F401
 from .api import advance_mu_t, bind_device_call, compute_window, VARIANT_AUTO, VARIANT_COLUMN, VARIANT_MARCH, LAUNCH_BESIDE_OTHERS  # noqa: F401
 from .api import host_cache_enable, host_invalidate, host_defer, host_fetch, host_stale, host_release, held_arrays  # noqa: F401
 from .api import host_set_devices, host_devices  # noqa: F401
@@ -30,3 +33,5 @@ from . import patch  # noqa: F401
 from . import wrfdump  # noqa: F401
 from . import ensemble  # noqa: F401
 from .ensemble import Ensemble, advance_mu_t_ensemble  # noqa: F401
+from . import diag  # noqa: F401
+from .diag import field_stats, compare  # noqa: F401

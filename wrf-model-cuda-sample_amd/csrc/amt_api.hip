@@ -39,6 +39,7 @@ extern "C" const char *amt_status_string(int s)
     case AMT_ERR_NO_DEVICE: return "no HIP device";
     case AMT_ERR_ALLOC: return "allocation failed";
     case AMT_ERR_COMM: return "RCCL error";
+    case AMT_ERR_NONFINITE: return "the non-finite guard found a NaN or Inf in ww, t or mu";
     default: return "unknown status";
     }
 }

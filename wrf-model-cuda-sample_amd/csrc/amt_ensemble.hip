@@ -15,19 +15,12 @@ extern "C" int amt_advance_mu_t_ensemble_device_f64(void *hip_stream, int varian
     return amt_device_call_ensemble<double>(hip_stream, variant, members, a);
 }
 
-// The bounds, flags, scalars, variant, stream and the 26 BASE pointers live in an amt_domain (so that amt_domain_args packs the
-// call); what that struct calls a field's count is ONE member's.
-struct amt_ensemble {
-    amt_domain d;
-    int members = 1;
-    size_t count(int f) const { return d.count(f) * (amt_field_rank(f) == 1 ? (size_t)1 : (size_t)members); }
-};
-
 extern "C" int amt_ensemble_destroy(amt_ensemble *e)
 {
     if (!e) return AMT_OK;
     amt_domain &d = e->d;
     DeviceScope scope(d.device);
+    amt_diag_release(&d);
     if (d.owns_fields)
         for (void *&q : d.field)
             if (q) { (void)hipFree(q); q = nullptr; }
@@ -177,10 +170,13 @@ static int amt_ensemble_step_t(amt_ensemble *e, int n_sweeps)
 {
     AmtArgs<T> a;
     amt_domain_args<T>(&e->d, a);
+    // an armed guard that already shows a finding: nothing is enqueued (no wait: the record is in host memory)
+    if (e->d.guard_every) { const int rc = amt_diag_guard_status("amt_ensemble_step", &e->d); if (rc) return rc; }
     for (int s = 0; s < n_sweeps; ++s) {
         // cyclic boundaries: every member's wrap cells in one launch in front of the sweep, on the same stream
         int rc = e->d.cyclic ? amt_cyclic_refresh_domain("amt_ensemble_step", &e->d, e->d.cyclic, e->members) : AMT_OK;
         if (rc == AMT_OK) rc = amt_device_call_ensemble<T>(e->d.stream, e->d.variant, e->members, a);
+        if (rc == AMT_OK && e->d.guard_every) rc = amt_diag_after_sweep("amt_ensemble_step", &e->d, e->members);
         if (rc) return rc;
     }
     return AMT_OK;
@@ -223,7 +219,7 @@ extern "C" int amt_ensemble_step_timed(amt_ensemble *e, int n_sweeps, float *ms_
     float ms = 0.f;
     AMT_HIP(hipEventElapsedTime(&ms, d.ev0, d.ev1));
     if (ms_total) *ms_total = ms;
-    return AMT_OK;
+    return d.guard_every ? amt_diag_guard_status("amt_ensemble_step_timed", &d) : AMT_OK;
 }
 
 extern "C" int amt_ensemble_sync(amt_ensemble *e)
@@ -231,7 +227,7 @@ extern "C" int amt_ensemble_sync(amt_ensemble *e)
     if (!e) return amt_fail(AMT_ERR_INVALID_ARG, "null ensemble");
     DeviceScope scope(e->d.device);
     AMT_HIP(hipStreamSynchronize(e->d.stream));
-    return AMT_OK;
+    return e->d.guard_every ? amt_diag_guard_status("amt_ensemble_sync", &e->d) : AMT_OK;
 }
 
 extern "C" void *amt_ensemble_field_ptr(amt_ensemble *e, int field)

@@ -124,6 +124,8 @@ struct DeviceScope {
 };
 }  // namespace
 
+struct AmtDiagState;              // workspace, result records and guard state of section (10) (amt_diag.hip)
+
 struct amt_domain {
     int dtype_bytes = 8;
     int periodic_x = 0, specified = 0, nested = 0;
@@ -139,12 +141,22 @@ struct amt_domain {
     int cyclic = 0;               // amt_cyclic_axes refreshed in front of every sweep (amt_domain_set_cyclic); 0 = off
     int placement_tries = 0;      // allocations of the state that were timed (amt_domain_create / amt_domain_tune_placement)
     float placement_ms[16] = {};  // sweep time on each (0: not tried)
+    int guard_every = 0;          // non-finite guard: check after every n-th sweep (amt_domain_set_guard); 0 = off
+    AmtDiagState *diag = nullptr; // made by the first call of section (10) on this handle, freed with it
     size_t count(int f) const
     {
         const size_t idim = ime - ims + 1, kdim = kme - kms + 1, jdim = jme - jms + 1;
         const int r = amt_field_rank(f);
         return r == 3 ? idim * kdim * jdim : r == 2 ? idim * jdim : kdim;
     }
+};
+
+// resident ensemble handle (amt_ensemble.hip).  The bounds, flags, scalars, variant, stream and the 26 BASE pointers live in an
+// amt_domain (so that amt_domain_args packs the call); what that struct calls a field's count is ONE member's.
+struct amt_ensemble {
+    amt_domain d;
+    int members = 1;
+    size_t count(int f) const { return d.count(f) * (amt_field_rank(f) == 1 ? (size_t)1 : (size_t)members); }
 };
 
 template <typename T>
@@ -172,3 +184,16 @@ inline void amt_domain_args(amt_domain *d, AmtArgs<T> &a)
 // ---------------------------------------------------------------------------
 int amt_cyclic_refresh_domain(const char *who, amt_domain *d, int axes, int members);
 int amt_cyclic_check_domain(const char *who, const amt_domain *d, int axes, int members);
+
+// ---------------------------------------------------------------------------
+// field statistics, comparison and the non-finite guard (amt_diag.hip, header section 10).  The steppers call these only
+// while a guard is armed (d->guard_every != 0): with it off they enqueue what they always did.
+//   amt_diag_guard_status: AMT_ERR_NONFINITE (with the text of amt_last_error) when the guard's host record shows a finding
+//                          NOW, else AMT_OK; reads page-locked host memory, never waits
+//   amt_diag_after_sweep:  one more sweep of `members` member-stacked patches was enqueued on d->stream; on every n-th the
+//                          three checks follow it on the same stream
+//   amt_diag_release:      frees d->diag (the handles' destroy)
+// ---------------------------------------------------------------------------
+int amt_diag_guard_status(const char *who, const amt_domain *d);
+int amt_diag_after_sweep(const char *who, amt_domain *d, int members);
+void amt_diag_release(amt_domain *d);

@@ -99,9 +99,14 @@ def advance_mu_t_ensemble(ww, ww_1, u, u_1, v, v_1, mu, mut, muave, muts, muu, m
     _lib.check(status)
 
 
-class Ensemble:
+class Ensemble(_lib.HandleDiag):
     """Resident ensemble handle (``amt_ensemble_*``).  ``Ensemble(b, members, ...)`` lets the library allocate the stacked
     arrays on the current device; ``Ensemble.wrap(arrays, b, ...)`` steps the caller's torch tensors in place."""
+
+    _PREFIX = "amt_ensemble"
+
+    def _members(self) -> int:
+        return self.members
 
     def __init__(self, b: _S.Bounds, members: int, config: GridConfig = GridConfig(), dtype=np.float64, *,
                  _fields=None, _stream=None, _keep=None):
@@ -174,11 +179,11 @@ class Ensemble:
                                                       gni + 2, gnk + 1, gnj + 2))
 
     def step(self, n_sweeps: int = 1) -> None:
-        _lib.check(self.L.amt_ensemble_step(self.handle, int(n_sweeps)))
+        self._check(self.L.amt_ensemble_step(self.handle, int(n_sweeps)))
 
     def step_timed(self, n_sweeps: int = 1) -> float:
         ms = ctypes.c_float()
-        _lib.check(self.L.amt_ensemble_step_timed(self.handle, int(n_sweeps), ctypes.byref(ms)))
+        self._check(self.L.amt_ensemble_step_timed(self.handle, int(n_sweeps), ctypes.byref(ms)))
         return float(ms.value)
 
     def set_cyclic(self, axes: int) -> None:
@@ -194,7 +199,7 @@ class Ensemble:
         _lib.check(self.L.amt_ensemble_cyclic_fill(self.handle, int(axes)))
 
     def sync(self) -> None:
-        _lib.check(self.L.amt_ensemble_sync(self.handle))
+        self._check(self.L.amt_ensemble_sync(self.handle))
 
     def field_ptr(self, name: str) -> int:
         return int(self.L.amt_ensemble_field_ptr(self.handle, _S.FIELD_ID[name]) or 0)

@@ -7,6 +7,24 @@ MODULE amt_c_binding
    implicit none
 
    integer(c_int), parameter :: AMT_OK = 0
+   integer(c_int), parameter :: AMT_ERR_NONFINITE = 7         ! the non-finite guard of header section 10 has a finding
+   ! enum amt_region (amt_domain_field_stats, amt_domain_compare and their ensemble twins)
+   integer(c_int), parameter :: AMT_REGION_WINDOW = 0, AMT_REGION_MEMORY = 1
+
+   ! the result records of header section 10; offsets count elements from the member's base
+   type, bind(C) :: amt_field_stats
+      integer(c_int64_t) :: count, n_nan, n_inf, first_nonfinite
+      real(c_double) :: min, max, max_abs, sum
+   end type
+   type, bind(C) :: amt_field_diff
+      integer(c_int64_t) :: count, n_diff, first_diff
+      real(c_double) :: max_abs_diff
+   end type
+   type, bind(C) :: amt_guard_report
+      integer(c_int64_t) :: sweeps_checked, sweep
+      integer(c_int32_t) :: field, member
+      integer(c_int64_t) :: offset, n_nonfinite
+   end type
    ! enum amt_slab_flags (amt_slab_create / amt_grid_create)
    integer(c_int), parameter :: AMT_SLAB_NO_OVERLAP = 1, AMT_SLAB_LOOPBACK = 2, AMT_SLAB_TRANSPORT_IPC = 4,  &
                                 AMT_SLAB_CYCLIC_X = 8, AMT_SLAB_CYCLIC_Y = 16
@@ -565,6 +583,95 @@ MODULE amt_c_binding
          import :: c_ptr, c_int
          type(c_ptr), value :: handle
          integer(c_int) :: axes
+      end function
+      ! (10) statistics, bit comparison and the non-finite guard.  Pointer level: a, b are device pointers, out is a HOST array
+      ! of `members` records; the call waits for hip_stream
+      function amt_stats_device_f32(hip_stream, a, rank, members, ims, ime, jms, jme, kms, kme,                         &
+                                    i0, i1, k0, k1, j0, j1, out) bind(C, name="amt_stats_device_f32") result(rc)
+         import :: c_ptr, c_int, amt_field_stats
+         type(c_ptr), value :: hip_stream, a
+         integer(c_int), value :: rank, members, ims, ime, jms, jme, kms, kme, i0, i1, k0, k1, j0, j1
+         type(amt_field_stats), intent(inout) :: out(*)
+         integer(c_int) :: rc
+      end function
+      function amt_stats_device_f64(hip_stream, a, rank, members, ims, ime, jms, jme, kms, kme,                         &
+                                    i0, i1, k0, k1, j0, j1, out) bind(C, name="amt_stats_device_f64") result(rc)
+         import :: c_ptr, c_int, amt_field_stats
+         type(c_ptr), value :: hip_stream, a
+         integer(c_int), value :: rank, members, ims, ime, jms, jme, kms, kme, i0, i1, k0, k1, j0, j1
+         type(amt_field_stats), intent(inout) :: out(*)
+         integer(c_int) :: rc
+      end function
+      function amt_compare_device_f32(hip_stream, a, b, rank, members, ims, ime, jms, jme, kms, kme,                    &
+                                      i0, i1, k0, k1, j0, j1, out) bind(C, name="amt_compare_device_f32") result(rc)
+         import :: c_ptr, c_int, amt_field_diff
+         type(c_ptr), value :: hip_stream, a, b
+         integer(c_int), value :: rank, members, ims, ime, jms, jme, kms, kme, i0, i1, k0, k1, j0, j1
+         type(amt_field_diff), intent(inout) :: out(*)
+         integer(c_int) :: rc
+      end function
+      function amt_compare_device_f64(hip_stream, a, b, rank, members, ims, ime, jms, jme, kms, kme,                    &
+                                      i0, i1, k0, k1, j0, j1, out) bind(C, name="amt_compare_device_f64") result(rc)
+         import :: c_ptr, c_int, amt_field_diff
+         type(c_ptr), value :: hip_stream, a, b
+         integer(c_int), value :: rank, members, ims, ime, jms, jme, kms, kme, i0, i1, k0, k1, j0, j1
+         type(amt_field_diff), intent(inout) :: out(*)
+         integer(c_int) :: rc
+      end function
+      ! handle level: region = AMT_REGION_WINDOW or AMT_REGION_MEMORY; an ensemble fills one record per member
+      function amt_domain_field_stats(handle, field, region, out) bind(C, name="amt_domain_field_stats") result(rc)
+         import :: c_ptr, c_int, amt_field_stats
+         type(c_ptr), value :: handle
+         integer(c_int), value :: field, region
+         type(amt_field_stats), intent(inout) :: out(*)
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_field_stats(handle, field, region, out) bind(C, name="amt_ensemble_field_stats") result(rc)
+         import :: c_ptr, c_int, amt_field_stats
+         type(c_ptr), value :: handle
+         integer(c_int), value :: field, region
+         type(amt_field_stats), intent(inout) :: out(*)
+         integer(c_int) :: rc
+      end function
+      function amt_domain_compare(handle_a, handle_b, field, region, out) bind(C, name="amt_domain_compare") result(rc)
+         import :: c_ptr, c_int, amt_field_diff
+         type(c_ptr), value :: handle_a, handle_b
+         integer(c_int), value :: field, region
+         type(amt_field_diff), intent(inout) :: out(*)
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_compare(handle_a, handle_b, field, region, out) bind(C, name="amt_ensemble_compare") result(rc)
+         import :: c_ptr, c_int, amt_field_diff
+         type(c_ptr), value :: handle_a, handle_b
+         integer(c_int), value :: field, region
+         type(amt_field_diff), intent(inout) :: out(*)
+         integer(c_int) :: rc
+      end function
+      ! every = 0: off; n >= 1: ww, t and mu are checked after every n-th sweep of amt_*_step; a finding makes amt_*_sync,
+      ! amt_*_step_timed and the next amt_*_step return AMT_ERR_NONFINITE
+      function amt_domain_set_guard(handle, every) bind(C, name="amt_domain_set_guard") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: every
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_set_guard(handle, every) bind(C, name="amt_ensemble_set_guard") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: every
+         integer(c_int) :: rc
+      end function
+      function amt_domain_guard_report(handle, out) bind(C, name="amt_domain_guard_report") result(rc)
+         import :: c_ptr, c_int, amt_guard_report
+         type(c_ptr), value :: handle
+         type(amt_guard_report), intent(inout) :: out
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_guard_report(handle, out) bind(C, name="amt_ensemble_guard_report") result(rc)
+         import :: c_ptr, c_int, amt_guard_report
+         type(c_ptr), value :: handle
+         type(amt_guard_report), intent(inout) :: out
+         integer(c_int) :: rc
       end function
    end interface
 

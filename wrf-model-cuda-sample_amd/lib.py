@@ -13,13 +13,45 @@ PKG_DIR = Path(__file__).resolve().parent
 _LIB_NAME = "libamt_advance_mu_t.so"
 
 # status codes of include/amt_advance_mu_t.h
-OK, ERR_HIP, ERR_PRECONDITION, ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_ALLOC, ERR_COMM = range(7)
+OK, ERR_HIP, ERR_PRECONDITION, ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_ALLOC, ERR_COMM, ERR_NONFINITE = range(8)
+
+REGION_WINDOW, REGION_MEMORY = 0, 1       # enum amt_region
 
 
 class AmtError(RuntimeError):
-    def __init__(self, status: int, message: str):
+    """``report``: the handle's ``GuardReport`` when the status is ERR_NONFINITE and a handle method raised it, else None."""
+
+    def __init__(self, status: int, message: str, report=None):
         super().__init__(f"amt status {status}: {message}")
         self.status = status
+        self.report = report
+
+
+class _Record(ctypes.Structure):
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+    def __repr__(self):
+        return f"{type(self).__name__}({', '.join(f'{k}={v!r}' for k, v in self.as_dict().items())})"
+
+
+class FieldStats(_Record):
+    """``amt_field_stats``"""
+    _fields_ = [("count", ctypes.c_int64), ("n_nan", ctypes.c_int64), ("n_inf", ctypes.c_int64),
+                ("first_nonfinite", ctypes.c_int64), ("min", ctypes.c_double), ("max", ctypes.c_double),
+                ("max_abs", ctypes.c_double), ("sum", ctypes.c_double)]
+
+
+class FieldDiff(_Record):
+    """``amt_field_diff``"""
+    _fields_ = [("count", ctypes.c_int64), ("n_diff", ctypes.c_int64), ("first_diff", ctypes.c_int64),
+                ("max_abs_diff", ctypes.c_double)]
+
+
+class GuardReport(_Record):
+    """``amt_guard_report``"""
+    _fields_ = [("sweeps_checked", ctypes.c_int64), ("sweep", ctypes.c_int64), ("field", ctypes.c_int32),
+                ("member", ctypes.c_int32), ("offset", ctypes.c_int64), ("n_nonfinite", ctypes.c_int64)]
 
 
 def library_path() -> Path:
@@ -141,6 +173,18 @@ SYMBOLS = {
     "amt_ensemble_cyclic_fill": (_I, [_P, _I]),
     "amt_ensemble_set_cyclic": (_I, [_P, _I]),
     "amt_ensemble_cyclic": (_I, [_P]),
+    "amt_stats_device_f32": (_I, [_P, _P, _I, _I] + [_I] * 12 + [ctypes.POINTER(FieldStats)]),
+    "amt_stats_device_f64": (_I, [_P, _P, _I, _I] + [_I] * 12 + [ctypes.POINTER(FieldStats)]),
+    "amt_compare_device_f32": (_I, [_P, _P, _P, _I, _I] + [_I] * 12 + [ctypes.POINTER(FieldDiff)]),
+    "amt_compare_device_f64": (_I, [_P, _P, _P, _I, _I] + [_I] * 12 + [ctypes.POINTER(FieldDiff)]),
+    "amt_domain_field_stats": (_I, [_P, _I, _I, ctypes.POINTER(FieldStats)]),
+    "amt_ensemble_field_stats": (_I, [_P, _I, _I, ctypes.POINTER(FieldStats)]),
+    "amt_domain_compare": (_I, [_P, _P, _I, _I, ctypes.POINTER(FieldDiff)]),
+    "amt_ensemble_compare": (_I, [_P, _P, _I, _I, ctypes.POINTER(FieldDiff)]),
+    "amt_domain_set_guard": (_I, [_P, _I]),
+    "amt_ensemble_set_guard": (_I, [_P, _I]),
+    "amt_domain_guard_report": (_I, [_P, ctypes.POINTER(GuardReport)]),
+    "amt_ensemble_guard_report": (_I, [_P, ctypes.POINTER(GuardReport)]),
     "amt_march_force_shape": (_I, [_I] * 7),
     "amt_march_rows_for": (_I, [ctypes.c_long, _I, _I, ctypes.c_long, _I, _I]),
     "amt_march_set_xchunk": (_I, [_I]),
@@ -180,3 +224,44 @@ def check(status: int) -> None:
         L = load_library()
         msg = L.amt_last_error().decode() or L.amt_status_string(status).decode()
         raise AmtError(status, msg)
+
+
+class HandleDiag:
+    """``field_stats / compare / set_guard / guard_report`` of a resident handle (header section 10).  The owning class names
+    its C functions' prefix (``amt_domain`` / ``amt_ensemble``) in ``_PREFIX`` and its member count in ``_members()``; its
+    stepping methods pass their status through ``_check`` so that an ERR_NONFINITE error carries the guard's report."""
+    _PREFIX = "amt_domain"
+
+    def _members(self) -> int:
+        return 1
+
+    def _fn(self, name: str):
+        return getattr(self.L, f"{self._PREFIX}_{name}")
+
+    def _check(self, status: int) -> None:
+        if status == ERR_NONFINITE:
+            msg = self.L.amt_last_error().decode()
+            raise AmtError(status, msg, report=self.guard_report())
+        check(status)
+
+    def field_stats(self, field: int, region: int = REGION_WINDOW):
+        """``FieldStats`` of ``field`` (enum amt_field) over ``region``; an ensemble returns a list, one per member."""
+        out = (FieldStats * self._members())()
+        check(self._fn("field_stats")(self.handle, int(field), int(region), out))
+        return list(out) if self._PREFIX == "amt_ensemble" else out[0]
+
+    def compare(self, other, field: int, region: int = REGION_MEMORY):
+        """``FieldDiff`` of this handle's ``field`` against ``other``'s (same dtype, bounds and member count)."""
+        out = (FieldDiff * self._members())()
+        check(self._fn("compare")(self.handle, other.handle, int(field), int(region), out))
+        return list(out) if self._PREFIX == "amt_ensemble" else out[0]
+
+    def set_guard(self, every: int) -> None:
+        """0: off.  n >= 1: ww, t and mu are checked for NaN / Inf after every n-th sweep of the handle's own stepping; the
+        first finding makes ``sync`` / ``step`` raise ``AmtError`` (status ERR_NONFINITE, ``.report`` set)."""
+        check(self._fn("set_guard")(self.handle, int(every)))
+
+    def guard_report(self) -> GuardReport:
+        out = GuardReport()
+        check(self._fn("guard_report")(self.handle, ctypes.byref(out)))
+        return out

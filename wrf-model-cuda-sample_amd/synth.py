@@ -190,7 +190,7 @@ def _fill_args(b: Bounds, name: str, gdims):
     return (idim, kdim, jdim, b.ims, b.kms - 1, b.jms, gni + 2, gnk + 1, gnj + 2), r
 
 
-class NativeDomain:
+class NativeDomain(_lib.HandleDiag):
     """Owner of a resident handle made by ``amt_domain_create`` (the C-ABI a Fortran or C host calls, placement sampling
     included) whose 26 device arrays torch tensors VIEW through ``__cuda_array_interface__``: a Python caller then holds
     exactly the memory a native host would.  Destroyed with the last tensor that views it."""
@@ -199,6 +199,18 @@ class NativeDomain:
         self.L = _lib.load_library()
         self.handle = ctypes.c_void_p()
         _lib.check(self.L.amt_domain_create(ctypes.byref(self.handle), itemsize, *config.as_ints(), *b.as_tuple()))
+
+    def step(self, n_sweeps: int = 1) -> None:
+        """``amt_domain_step``: asynchronous on the handle's stream."""
+        self._check(self.L.amt_domain_step(self.handle, int(n_sweeps)))
+
+    def step_timed(self, n_sweeps: int = 1) -> float:
+        ms = ctypes.c_float()
+        self._check(self.L.amt_domain_step_timed(self.handle, int(n_sweeps), ctypes.byref(ms)))
+        return float(ms.value)
+
+    def sync(self) -> None:
+        self._check(self.L.amt_domain_sync(self.handle))
 
     def placement_ms(self):
         """Sweep time (ms) on every allocation of the state that amt_domain_create timed; [] when it did not sample."""
