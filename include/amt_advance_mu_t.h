@@ -393,7 +393,14 @@ enum amt_slab_flags {
      * is involved: the refresh kernel of (9) runs on the domain's stream in front of every sweep.  Preconditions as in (9);
      * together with AMT_SLAB_LOOPBACK: AMT_ERR_INVALID_ARG. */
     AMT_SLAB_CYCLIC_X = 8,
-    AMT_SLAB_CYCLIC_Y = 16
+    AMT_SLAB_CYCLIC_Y = 16,
+    /* Section (11): the HOST moves the halos.  The library packs one contiguous message per side, the host carries the
+     * messages with whatever it owns (MPI), the library unpacks.  unique_id may be NULL, creation is not collective, no RCCL
+     * and no shared-memory block are involved, any number of such handles may live in one process and on one device; the
+     * AMT_SLAB_TRANSPORT environment override does not apply.  Together with AMT_SLAB_LOOPBACK: AMT_ERR_INVALID_ARG.
+     * AMT_SLAB_NO_OVERLAP and the cyclic flags work as with the other transports. */
+    AMT_SLAB_TRANSPORT_EXTERNAL = 32,
+    AMT_SLAB_EXTERNAL_HOST_BUFFERS = 64      /* with EXTERNAL: the messages lie in page-locked host memory */
 };
 typedef struct amt_slab amt_slab;
 
@@ -419,7 +426,7 @@ int amt_slab_exchange(amt_slab *slab);       /* the halo exchange alone         
 int amt_slab_step(amt_slab *slab, int n_sweeps);             /* asynchronous                      */
 int amt_slab_step_timed(amt_slab *slab, int n_sweeps, float *ms_total);
 int amt_slab_sync(amt_slab *slab);               /* AMT_ERR_COMM if a device-side wait for a neighbour gave up (IPC) */
-const char *amt_slab_transport(const amt_slab *slab);        /* "rccl", "ipc", or "none" (a world of one)  */
+const char *amt_slab_transport(const amt_slab *slab);        /* "rccl", "ipc", "external" (11), or "none" (no neighbour) */
 /* how the IPC transport pulls: "copy engine" (between GPUs: hipMemcpyAsync per row) or "fused kernel" (ranks that share a device,
  * loopback: one kernel waits, pulls and posts -- a peer copy is a blit kernel there anyway); "" with RCCL */
 const char *amt_slab_pull_mode(const amt_slab *slab);
@@ -733,6 +740,69 @@ int amt_domain_set_guard(amt_domain *d, int every);
 int amt_ensemble_set_guard(amt_ensemble *e, int every);
 int amt_domain_guard_report(amt_domain *d, amt_guard_report *out);
 int amt_ensemble_guard_report(amt_ensemble *e, amt_guard_report *out);
+
+/* ------------------------------------------------------------------------
+ * (11) Host-owned halo exchange (AMT_SLAB_TRANSPORT_EXTERNAL of (5)): for a host that has its own communicator and halo
+ *      layer (MPI, GPU-aware or not).  The library does not link or detect MPI.  Per side that has a neighbour the handle
+ *      owns ONE send and ONE receive buffer (base 256-byte aligned; device memory, or page-locked host memory with
+ *      AMT_SLAB_EXTERNAL_HOST_BUFFERS); one kernel launch packs all sends, one unpacks all receives.
+ *      CONTENT, fixed: a peer that is not this library can produce it.  ilo..ihi, jlo..jhi: the patch's first / last column
+ *      and row -- its..ite, jts..jte, in a cyclic direction the compute window's edges (a last patch may end at ide-1 or at
+ *      ide); ni = ihi-ilo+1, nj = jhi-jlo+1; levels are every memory level kms..kme; elements travel as bits.
+ *        send towards BELOW = the neighbour's recv from ABOVE: row jlo of v, v_1, t_1 (each: i fastest over ilo..ihi, then
+ *                             k), then row jlo of muv, msfvx_inv (i over ilo..ihi)                   (3 kdim + 2) ni elements
+ *        send towards ABOVE = recv from BELOW:                 row jhi of t_1                                  kdim ni
+ *        send towards LEFT  = recv from RIGHT: column ilo of u, u_1, t_1 (each: k fastest, then j over jlo..jhi), then
+ *                             column ilo of muu, msfuy (j over jlo..jhi)                             (3 kdim + 2) nj
+ *        send towards RIGHT = recv from LEFT:                  column ihi of t_1                               kdim nj
+ *      Received data lands in row jhi+1 / jlo-1 and column ihi+1 / ilo-1, columns ilo..ihi / rows jlo..jhi only: the cells
+ *      outside (the corners) are never written -- the stencil reads no diagonal.  send_bytes of a rank towards a side equals
+ *      recv_bytes of its neighbour from the opposite side.
+ *      SWEEP: amt_grid_step_begin -> [amt_grid_halo_wait] -> amt_grid_step_end; any other order (end without begin, begin
+ *      twice, a second wait, pack / unpack inside an open sweep) is AMT_ERR_INVALID_ARG before any device call, and so are
+ *      amt_grid_step, _step_timed, _exchange, _max and _barrier on such a handle.
+ *        begin  (asynchronous) on the domain's stream: the self-wrap refresh of a cyclic direction with one rank, the pack,
+ *               the event "packed", then the interior cells (planned on their own: the whole chip).
+ *        wait   (host) returns when "packed" of this sweep has happened -- the send buffers are readable -- and the unpack
+ *               of the previous sweep has run -- the receive buffers are writable.  The interior keeps running meanwhile.
+ *        end    (asynchronous) on the communication stream behind "packed": the unpack, the boundary rows and columns, the
+ *               join into the domain's stream.
+ *      With AMT_SLAB_NO_OVERLAP begin is refresh, pack, "packed"; end is the unpack and the whole patch as one launch on the
+ *      domain's stream.  A patch without any neighbour: begin is the plain launch, wait and end enqueue nothing, no message.
+ *      CONTRACT: the host completes its sends and its receives of sweep n between amt_grid_halo_wait and amt_grid_step_end
+ *      of sweep n (with a stream-ordered transport it may skip the wait and order its copies itself).
+ *      amt_grid_halo_pack / _unpack are the two halves of amt_grid_exchange without any compute, both asynchronous on the
+ *      domain's stream: pack, amt_grid_sync, move the messages, unpack.
+ * ------------------------------------------------------------------------ */
+typedef struct amt_halo_message {
+    int side;            /* AMT_SIDE_BELOW / ABOVE / LEFT / RIGHT (enum amt_sides) */
+    int peer;            /* rank rj*pi+ri of the neighbour; with two ranks in a cyclic direction two sides name one peer: tag by side */
+    void *send;  size_t send_bytes;
+    void *recv;  size_t recv_bytes;
+    int on_host;         /* 1: page-locked host memory (AMT_SLAB_EXTERNAL_HOST_BUFFERS) */
+} amt_halo_message;
+/* the messages of a handle, in the order BELOW, ABOVE, LEFT, RIGHT; *n = their number (0..4), also when it exceeds cap
+ * (then AMT_ERR_INVALID_ARG and nothing is written); out may be NULL with cap = 0 */
+int amt_grid_halo_messages(amt_grid *grid, amt_halo_message *out, int cap, int *n);
+int amt_slab_halo_messages(amt_slab *slab, amt_halo_message *out, int cap, int *n);
+/* The same list from the shape alone -- host arithmetic, no device, no handle: side, peer, send_bytes, recv_bytes; the
+ * pointers are NULL.  flags: enum amt_slab_flags (EXTERNAL is implied); the precondition errors are those of creation. */
+int amt_halo_plan(int dtype_bytes, int periodic_x, int specified, int nested,
+                  int ids, int ide, int jds, int jde, int kde,
+                  int ims, int ime, int jms, int jme, int kms, int kme,
+                  int its, int ite, int jts, int jte, int kts, int kte,
+                  int ri, int rj, int pi, int pj, int flags,
+                  amt_halo_message *out, int cap, int *n);
+int amt_grid_step_begin(amt_grid *grid);     /* asynchronous */
+int amt_grid_halo_wait(amt_grid *grid);      /* host wait: send buffers readable AND recv buffers writable */
+int amt_grid_step_end(amt_grid *grid);       /* asynchronous; the host's receives of this sweep are complete */
+int amt_grid_halo_pack(amt_grid *grid);
+int amt_grid_halo_unpack(amt_grid *grid);
+int amt_slab_step_begin(amt_slab *slab);
+int amt_slab_halo_wait(amt_slab *slab);
+int amt_slab_step_end(amt_slab *slab);
+int amt_slab_halo_pack(amt_slab *slab);
+int amt_slab_halo_unpack(amt_slab *slab);
 
 #ifdef __cplusplus
 }

@@ -33,6 +33,15 @@ struct amt_grid {
     unsigned long long packs = 0;                           // exchanges begun (what AMT_TEST_FAULT skip_pack / skip_unpack count)
     // packed columns: what goes to the left / right neighbour, what came from the right / left one
     void *to_left = nullptr, *to_right = nullptr, *from_right = nullptr, *from_left = nullptr;
+    // Host-owned exchange (AMT_SLAB_TRANSPORT_EXTERNAL; header section 11): no AmtExchange; one send and
+    // one receive message per side with a neighbour (order BELOW, ABOVE, LEFT, RIGHT), all carved out of ONE allocation at
+    // 256-byte steps; phase: 0 = no sweep open, 1 = begun, 2 = begun and waited for.
+    bool external = false, host_buffers = false;
+    int phase = 0;
+    int n_msg = 0;
+    amt_halo_message msg[4] = {};
+    void *msg_block = nullptr;
+    hipEvent_t packed = nullptr, unpacked = nullptr;
 };
 struct amt_slab {
     amt_grid g;
@@ -334,21 +343,34 @@ void grid_teardown(amt_grid *g)
     g->xchg = nullptr;
     for (hipStream_t st : {g->col_stream[0], g->col_stream[1]})
         if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-    for (hipEvent_t e : {g->inputs_final, g->edges_done, g->t0, g->t1, g->halos_in, g->col_done[0], g->col_done[1]})
+    for (hipEvent_t e : {g->inputs_final, g->edges_done, g->t0, g->t1, g->halos_in, g->col_done[0], g->col_done[1], g->packed, g->unpacked})
         if (e) (void)hipEventDestroy(e);
     if (g->comm_stream) (void)hipStreamDestroy(g->comm_stream);
     for (void *q : {g->to_left, g->to_right, g->from_right, g->from_left})
         if (q) (void)hipFree(q);
+    if (g->msg_block) (void)(g->host_buffers ? hipHostFree(g->msg_block) : hipFree(g->msg_block));
+    g->msg_block = nullptr;
 }
 
-// loop_i / loop_j: one-rank test mode -- the rank is its own neighbour across i / across j
-int grid_setup(amt_grid *g, amt_domain *dom, int ri, int rj, int pi, int pj, const void *unique_id, int flags, bool loop_i, bool loop_j)
+// Who the neighbours are and whether the shape admits the flags: host arithmetic only, nothing of the device is touched (what
+// amt_grid_create and the planner amt_halo_plan share).  loop_i / loop_j: one-rank test mode -- the rank is its own neighbour
+// across i / across j.  id_given: the caller has a communicator id (a host-owned exchange needs none).
+int grid_topology(amt_grid *g, amt_domain *dom, int ri, int rj, int pi, int pj, bool id_given, int flags, bool loop_i, bool loop_j)
 {
     if (!dom || pi < 1 || pj < 1 || ri < 0 || ri >= pi || rj < 0 || rj >= pj) return amt_fail(AMT_ERR_INVALID_ARG, "bad patch index");
     const int world = pi * pj, rank = rj * pi + ri;
+    const bool external = (flags & AMT_SLAB_TRANSPORT_EXTERNAL) != 0;
+    if (external && (loop_i || loop_j || (flags & AMT_SLAB_LOOPBACK)))
+        return amt_fail(AMT_ERR_INVALID_ARG, "AMT_SLAB_LOOPBACK cannot be combined with AMT_SLAB_TRANSPORT_EXTERNAL: the host is the transport");
+    if (external && (flags & AMT_SLAB_TRANSPORT_IPC))
+        return amt_fail(AMT_ERR_INVALID_ARG, "AMT_SLAB_TRANSPORT_IPC and AMT_SLAB_TRANSPORT_EXTERNAL name two transports");
+    if (!external && (flags & AMT_SLAB_EXTERNAL_HOST_BUFFERS))
+        return amt_fail(AMT_ERR_INVALID_ARG, "AMT_SLAB_EXTERNAL_HOST_BUFFERS is an option of AMT_SLAB_TRANSPORT_EXTERNAL");
     if ((loop_i || loop_j) && world != 1) return amt_fail(AMT_ERR_INVALID_ARG, "loopback is a one-rank test mode");
-    const bool comm_needed = world > 1 || loop_i || loop_j;
-    if (comm_needed && !unique_id) return amt_fail(AMT_ERR_INVALID_ARG, "a communicator needs the unique id");
+    const bool comm_needed = !external && (world > 1 || loop_i || loop_j);
+    if (comm_needed && !id_given) return amt_fail(AMT_ERR_INVALID_ARG, "a communicator needs the unique id");
+    g->external = external;
+    g->host_buffers = external && (flags & AMT_SLAB_EXTERNAL_HOST_BUFFERS) != 0;
     g->dom = dom; g->ri = ri; g->rj = rj; g->pi = pi; g->pj = pj; g->rank = rank; g->world = world;
     g->overlap = !(flags & AMT_SLAB_NO_OVERLAP);
     const bool cyc_x = (flags & AMT_SLAB_CYCLIC_X) != 0, cyc_y = (flags & AMT_SLAB_CYCLIC_Y) != 0;
@@ -379,8 +401,242 @@ int grid_setup(amt_grid *g, amt_domain *dom, int ri, int rj, int pi, int pj, con
         return amt_fail(AMT_ERR_PRECONDITION, "a patch holds one halo row below jts and above jte");
     if ((g->left >= 0 || g->right >= 0) && (ec.ilo - 1 < dom->ims || ec.ihi + 1 > dom->ime))
         return amt_fail(AMT_ERR_PRECONDITION, "a patch holds one halo column left of its and right of ite");
+    return AMT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The host-owned exchange (AMT_SLAB_TRANSPORT_EXTERNAL; header section 11)
+// ---------------------------------------------------------------------------
+// side, peer and the byte counts of the messages of g (order BELOW, ABOVE, LEFT, RIGHT); pointers NULL.  Host arithmetic.
+int halo_plan(const amt_grid *g, amt_halo_message out[4])
+{
+    const amt_domain *d = g->dom;
+    const EdgeCells ec = edge_cells(g);
+    const size_t kdim = d->kme - d->kms + 1, es = (size_t)d->dtype_bytes;
+    const size_t ni = ec.ihi >= ec.ilo ? ec.ihi - ec.ilo + 1 : 0, nj = ec.jhi >= ec.jlo ? ec.jhi - ec.jlo + 1 : 0;
+    const size_t five_rows = (3 * kdim + 2) * ni * es, one_row = kdim * ni * es;        // v, v_1, t_1, muv, msfvx_inv / t_1
+    const size_t five_cols = (3 * kdim + 2) * nj * es, one_col = kdim * nj * es;        // u, u_1, t_1, muu, msfuy / t_1
+    int n = 0;
+    auto add = [&](int side, int peer, size_t send, size_t recv) {
+        if (peer < 0) return;
+        out[n] = amt_halo_message{side, peer, nullptr, send, nullptr, recv, g->host_buffers ? 1 : 0};
+        ++n;
+    };
+    add(AMT_SIDE_BELOW, g->below, five_rows, one_row);
+    add(AMT_SIDE_ABOVE, g->above, one_row, five_rows);
+    add(AMT_SIDE_LEFT, g->left, five_cols, one_col);
+    add(AMT_SIDE_RIGHT, g->right, one_col, five_cols);
+    return n;
+}
+
+int external_buffers(amt_grid *g)
+{
+    g->n_msg = halo_plan(g, g->msg);
+    auto step = [](size_t bytes) { return (bytes + 255) / 256 * 256; };
+    size_t total = 0;
+    for (int m = 0; m < g->n_msg; ++m) total += step(g->msg[m].send_bytes) + step(g->msg[m].recv_bytes);
+    if (total == 0) return AMT_OK;
+    // hipMalloc and hipHostMalloc return bases aligned far beyond 256 bytes
+    const hipError_t e = g->host_buffers ? hipHostMalloc(&g->msg_block, total, hipHostMallocDefault) : hipMalloc(&g->msg_block, total);
+    if (e != hipSuccess) {
+        g->msg_block = nullptr;
+        return amt_fail(e == hipErrorOutOfMemory ? AMT_ERR_ALLOC : AMT_ERR_HIP, "amt_grid_create: the halo messages (%zu bytes): %s", total, hipGetErrorString(e));
+    }
+    char *at = static_cast<char *>(g->msg_block);
+    for (int m = 0; m < g->n_msg; ++m) {
+        g->msg[m].send = at; at += step(g->msg[m].send_bytes);
+        g->msg[m].recv = at; at += step(g->msg[m].recv_bytes);
+    }
+    return AMT_OK;
+}
+
+// One launch for everything the patch sends (scatter = false: rows jlo / jhi and columns ilo / ihi into the send messages) or
+// for everything that arrived (true: the receive messages into rows jhi+1 / jlo-1 and columns ihi+1 / ilo-1).
+int external_move(amt_grid *g, hipStream_t stream, bool scatter)
+{
+    amt_domain *d = g->dom;
+    const EdgeCells ec = edge_cells(g);
+    const long idim = d->ime - d->ims + 1, kdim = d->kme - d->kms + 1;
+    const long ni = ec.ihi - ec.ilo + 1, nj = ec.jhi - ec.jlo + 1;
+    if (ni < 1 || nj < 1) return AMT_OK;
+    const size_t es = (size_t)d->dtype_bytes;
+    AmtHaloJob jobs[AMT_HALO_MAX_JOBS];
+    int n = 0;
+    // element (i, kms, j) of a 3-D field / (i, j) of a 2-D one
+    auto at = [&](int f, int i, int j) {
+        const long off = ((long)(j - d->jms) * (amt_field_rank(f) == 3 ? kdim : 1)) * idim + (i - d->ims);
+        return static_cast<char *>(d->field[f]) + (size_t)off * es;
+    };
+    auto rows = [&](const int *fields, int count, int j, void *msg) {
+        char *m = static_cast<char *>(msg);
+        for (int q = 0; q < count; ++q) {
+            const long runs = amt_field_rank(fields[q]) == 3 ? kdim : 1;
+            jobs[n++] = AmtHaloJob{at(fields[q], ec.ilo, j), m, runs, (int)ni};
+            m += (size_t)(runs * ni) * es;
+        }
+    };
+    auto cols = [&](const int *fields, int count, int i, void *msg) {
+        char *m = static_cast<char *>(msg);
+        for (int q = 0; q < count; ++q) {
+            const long runs = (amt_field_rank(fields[q]) == 3 ? kdim : 1) * nj;
+            jobs[n++] = AmtHaloJob{at(fields[q], i, ec.jlo), m, runs, 1};
+            m += (size_t)runs * es;
+        }
+    };
+    for (int k = 0; k < g->n_msg; ++k) {
+        const amt_halo_message &m = g->msg[k];
+        switch (m.side) {
+        case AMT_SIDE_BELOW:
+            if (scatter) rows(kRowsFromBelow, 1, ec.jlo - 1, m.recv); else rows(kRowsFromAbove, 5, ec.jlo, m.send);
+            break;
+        case AMT_SIDE_ABOVE:
+            if (scatter) rows(kRowsFromAbove, 5, ec.jhi + 1, m.recv); else rows(kRowsFromBelow, 1, ec.jhi, m.send);
+            break;
+        case AMT_SIDE_LEFT:
+            if (scatter) cols(kColsFromLeft, 1, ec.ilo - 1, m.recv); else cols(kColsFromRight, 5, ec.ilo, m.send);
+            break;
+        default:
+            if (scatter) cols(kColsFromRight, 5, ec.ihi + 1, m.recv); else cols(kColsFromLeft, 1, ec.ihi, m.send);
+            break;
+        }
+    }
+    return amt_halo_launch(stream, d->dtype_bytes, scatter, idim, jobs, n);
+}
+
+int external_only(const amt_grid *g, const char *who)
+{
+    if (g->external) return AMT_OK;
+    return amt_fail(AMT_ERR_INVALID_ARG, "%s needs a handle made with AMT_SLAB_TRANSPORT_EXTERNAL", who);
+}
+
+int not_for_external(const amt_grid *g, const char *who)
+{
+    if (!g->external) return AMT_OK;
+    return amt_fail(AMT_ERR_INVALID_ARG, "%s: the host moves this handle's halos (AMT_SLAB_TRANSPORT_EXTERNAL): call amt_grid_step_begin / "
+                    "amt_grid_halo_wait / amt_grid_step_end (amt_slab_*) per sweep, or amt_grid_halo_pack / amt_grid_halo_unpack", who);
+}
+
+// refresh (a cyclic direction with one rank), pack, "packed" -- on the domain's stream, where the inputs are final
+int external_pack(amt_grid *g, const char *who)
+{
+    amt_domain *d = g->dom;
+    int rc = g->self_wrap ? amt_cyclic_refresh_domain(who, d, g->self_wrap, 1) : AMT_OK;
+    if (rc == AMT_OK) rc = external_move(g, d->stream, false);
+    if (rc) return rc;
+    AMT_HIP(hipEventRecord(g->packed, d->stream));
+    return AMT_OK;
+}
+
+template <typename T>
+int external_begin_t(amt_grid *g)
+{
+    amt_domain *d = g->dom;
+    const EdgeCells ec = edge_cells(g);
+    const bool lo = g->below >= 0, hi = g->above >= 0, lf = g->left >= 0, rt = g->right >= 0;
+    if (g->n_msg == 0) {                                                   // no neighbour at all: the plain launch
+        const int rc = g->self_wrap ? amt_cyclic_refresh_domain("amt_grid_step_begin", d, g->self_wrap, 1) : AMT_OK;
+        return rc ? rc : grid_tile<T>(g, d->stream, ec.ilo, ec.ihi, ec.jlo, ec.jhi);
+    }
+    const int rc = external_pack(g, "amt_grid_step_begin");
+    if (rc || !g->overlap) return rc;
+    // the interior on its own, the launcher's best plan: nothing of the exchange holds a compute unit beside it
+    return grid_tile<T>(g, d->stream, ec.ilo + (lf ? 1 : 0), ec.ihi - (rt ? 1 : 0), ec.jlo + (lo ? 1 : 0), ec.jhi - (hi ? 1 : 0));
+}
+
+template <typename T>
+int external_end_t(amt_grid *g)
+{
+    amt_domain *d = g->dom;
+    if (g->n_msg == 0) return AMT_OK;
+    const EdgeCells ec = edge_cells(g);
+    const bool lo = g->below >= 0, hi = g->above >= 0, lf = g->left >= 0, rt = g->right >= 0;
+    if (!g->overlap) {
+        int rc = external_move(g, d->stream, true);
+        if (rc) return rc;
+        AMT_HIP(hipEventRecord(g->unpacked, d->stream));
+        return grid_tile<T>(g, d->stream, ec.ilo, ec.ihi, ec.jlo, ec.jhi);
+    }
+    const AmtWindow wclip = amt_window(d->periodic_x, d->specified, d->nested, d->ids, d->ide, d->jds, d->jde,
+                                       ec.ilo, ec.ihi, ec.jlo, ec.jhi, d->kts, d->kte);
+    const bool unclipped = wclip.j_start == ec.jlo && wclip.j_end == ec.jhi;
+    AMT_HIP(hipStreamWaitEvent(g->comm_stream, g->packed, 0));
+    int rc = external_move(g, g->comm_stream, true);
+    if (rc == AMT_OK && hipEventRecord(g->unpacked, g->comm_stream) != hipSuccess)
+        rc = amt_fail(AMT_ERR_HIP, "amt_grid_step_end: cannot record the unpack: %s", hipGetErrorString(hipGetLastError()));
+    if (rc == AMT_OK) rc = grid_edges<T>(g, g->comm_stream, lo, hi, lf, rt, unclipped, ec.jlo + (lo ? 1 : 0), ec.jhi - (hi ? 1 : 0));
+    (void)hipEventRecord(g->edges_done, g->comm_stream);                   // also after an error: the streams never stay apart
+    (void)hipStreamWaitEvent(d->stream, g->edges_done, 0);
+    return rc;
+}
+
+int external_begin(amt_grid *g)
+{
+    int rc = external_only(g, "amt_grid_step_begin");
+    if (rc) return rc;
+    if (g->phase != 0) return amt_fail(AMT_ERR_INVALID_ARG, "amt_grid_step_begin: the previous sweep is still open (amt_grid_step_end closes it)");
+    DeviceScope scope(g->dom->device);
+    rc = g->dom->dtype_bytes == 8 ? external_begin_t<double>(g) : external_begin_t<float>(g);
+    if (rc == AMT_OK) g->phase = 1;
+    return rc;
+}
+
+int external_wait(amt_grid *g)
+{
+    int rc = external_only(g, "amt_grid_halo_wait");
+    if (rc) return rc;
+    if (g->phase != 1) return amt_fail(AMT_ERR_INVALID_ARG, "amt_grid_halo_wait: once per sweep, between amt_grid_step_begin and amt_grid_step_end");
+    g->phase = 2;
+    if (g->n_msg == 0) return AMT_OK;
+    DeviceScope scope(g->dom->device);
+    AMT_HIP(hipEventSynchronize(g->packed));        // this sweep's send messages are complete
+    AMT_HIP(hipEventSynchronize(g->unpacked));      // the previous sweep's receive messages have been read (at once before the first)
+    return AMT_OK;
+}
+
+int external_end(amt_grid *g)
+{
+    int rc = external_only(g, "amt_grid_step_end");
+    if (rc) return rc;
+    if (g->phase == 0) return amt_fail(AMT_ERR_INVALID_ARG, "amt_grid_step_end without amt_grid_step_begin");
+    DeviceScope scope(g->dom->device);
+    g->phase = 0;
+    return g->dom->dtype_bytes == 8 ? external_end_t<double>(g) : external_end_t<float>(g);
+}
+
+int external_pack_only(amt_grid *g, bool unpack)
+{
+    const char *who = unpack ? "amt_grid_halo_unpack" : "amt_grid_halo_pack";
+    int rc = external_only(g, who);
+    if (rc) return rc;
+    if (g->phase != 0) return amt_fail(AMT_ERR_INVALID_ARG, "%s inside an open sweep (amt_grid_step_begin packs, amt_grid_step_end unpacks)", who);
+    if (g->n_msg == 0 && !g->self_wrap) return AMT_OK;
+    DeviceScope scope(g->dom->device);
+    if (!unpack) return external_pack(g, who);
+    rc = external_move(g, g->dom->stream, true);
+    if (rc) return rc;
+    AMT_HIP(hipEventRecord(g->unpacked, g->dom->stream));
+    return AMT_OK;
+}
+
+int external_messages(amt_grid *g, amt_halo_message *out, int cap, int *n)
+{
+    if (!n || cap < 0 || (cap > 0 && !out)) return amt_fail(AMT_ERR_INVALID_ARG, "amt_grid_halo_messages: bad argument");
+    const int rc = external_only(g, "amt_grid_halo_messages");
+    if (rc) return rc;
+    *n = g->n_msg;
+    if (g->n_msg > cap) return amt_fail(AMT_ERR_INVALID_ARG, "amt_grid_halo_messages: %d messages, room for %d", g->n_msg, cap);
+    for (int m = 0; m < g->n_msg; ++m) out[m] = g->msg[m];
+    return AMT_OK;
+}
+
+int grid_setup(amt_grid *g, amt_domain *dom, int ri, int rj, int pi, int pj, const void *unique_id, int flags, bool loop_i, bool loop_j)
+{
+    int rc = grid_topology(g, dom, ri, rj, pi, pj, unique_id != nullptr, flags, loop_i, loop_j);
+    if (rc) return rc;
+    const int rank = g->rank, world = g->world;
+    const EdgeCells ec = edge_cells(g);
     int transport = (flags & AMT_SLAB_TRANSPORT_IPC) ? AMT_XCHG_IPC : AMT_XCHG_RCCL;
-    if (const char *e = getenv("AMT_SLAB_TRANSPORT")) {                  // hosts that cannot pass the flag (the Fortran drivers)
+    if (const char *e = g->external ? nullptr : getenv("AMT_SLAB_TRANSPORT")) {                  // hosts that cannot pass the flag (the Fortran drivers)
         if (!strcmp(e, "ipc")) transport = AMT_XCHG_IPC;
         else if (!strcmp(e, "rccl")) transport = AMT_XCHG_RCCL;
         else if (*e) return amt_fail(AMT_ERR_INVALID_ARG, "AMT_SLAB_TRANSPORT must be rccl or ipc, not '%s'", e);
@@ -399,6 +655,13 @@ int grid_setup(amt_grid *g, amt_domain *dom, int ri, int rj, int pi, int pj, con
             if (e == hipSuccess) e = hipStreamCreateWithPriority(st, hipStreamNonBlocking, prio_high);
         for (hipEvent_t *ev : {&g->halos_in, &g->col_done[0], &g->col_done[1]})
             if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+    }
+    if (g->external) {
+        // the host is the transport: its messages instead of the column buffers and the exchange engine
+        for (hipEvent_t *ev : {&g->packed, &g->unpacked})
+            if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+        if (e != hipSuccess) return amt_fail(AMT_ERR_HIP, "amt_grid_create: %s", hipGetErrorString(e));
+        return external_buffers(g);
     }
     const ColumnPlan cp = column_plan(dom);
     if (e == hipSuccess && g->left >= 0) e = hipMalloc(&g->to_left, cp.bytes_from_right());
@@ -427,6 +690,7 @@ int grid_setup(amt_grid *g, amt_domain *dom, int ri, int rj, int pi, int pj, con
 
 int grid_exchange_only(amt_grid *g)
 {
+    if (const int no = not_for_external(g, "amt_grid_exchange")) return no;
     DeviceScope scope(g->dom->device);
     AMT_HIP(hipEventRecord(g->inputs_final, g->dom->stream));
     AMT_HIP(hipStreamWaitEvent(g->comm_stream, g->inputs_final, 0));
@@ -443,12 +707,14 @@ int grid_exchange_only(amt_grid *g)
 
 int grid_step(amt_grid *g, int n_sweeps)
 {
+    if (const int no = not_for_external(g, "amt_grid_step")) return no;
     DeviceScope scope(g->dom->device);
     return g->dom->dtype_bytes == 8 ? grid_step_t<double>(g, n_sweeps) : grid_step_t<float>(g, n_sweeps);
 }
 
 int grid_step_timed(amt_grid *g, int n_sweeps, float *ms_total)
 {
+    if (const int no = not_for_external(g, "amt_grid_step_timed")) return no;
     DeviceScope scope(g->dom->device);
     AMT_HIP(hipEventRecord(g->t0, g->dom->stream));
     int rc = grid_step(g, n_sweeps);
@@ -473,11 +739,13 @@ long grid_halo_bytes(const amt_grid *g)
 {
     size_t sent = 0, received = 0;
     amt_exchange_bytes(g->xchg, &sent, &received);
+    for (int m = 0; m < g->n_msg; ++m) { sent += g->msg[m].send_bytes; received += g->msg[m].recv_bytes; }      // host-owned exchange
     return (long)(sent + received);
 }
 
 const char *grid_transport(const amt_grid *g)
 {
+    if (g->external) return g->n_msg ? "external" : "none";
     if (!amt_exchange_active(g->xchg)) return "none";
     return amt_exchange_transport(g->xchg) == AMT_XCHG_IPC ? "ipc" : "rccl";
 }
@@ -487,6 +755,7 @@ const char *grid_transport(const amt_grid *g)
 // collective.
 int grid_max(amt_grid *g, double *x)
 {
+    if (g->external) return amt_fail(AMT_ERR_INVALID_ARG, "amt_grid_max / amt_grid_barrier: the host owns this handle's communicator (AMT_SLAB_TRANSPORT_EXTERNAL)");
     DeviceScope scope(g->dom->device);
     AMT_HIP(hipStreamSynchronize(g->dom->stream));
     AMT_HIP(hipStreamSynchronize(g->comm_stream));
@@ -546,6 +815,35 @@ extern "C" int amt_grid_set_skew_us(amt_grid *g, int microseconds)
     return AMT_OK;
 }
 
+extern "C" int amt_grid_halo_messages(amt_grid *g, amt_halo_message *out, int cap, int *n) { return g ? external_messages(g, out, cap, n) : amt_fail(AMT_ERR_INVALID_ARG, "null grid"); }
+extern "C" int amt_grid_step_begin(amt_grid *g) { return g ? external_begin(g) : amt_fail(AMT_ERR_INVALID_ARG, "null grid"); }
+extern "C" int amt_grid_halo_wait(amt_grid *g) { return g ? external_wait(g) : amt_fail(AMT_ERR_INVALID_ARG, "null grid"); }
+extern "C" int amt_grid_step_end(amt_grid *g) { return g ? external_end(g) : amt_fail(AMT_ERR_INVALID_ARG, "null grid"); }
+extern "C" int amt_grid_halo_pack(amt_grid *g) { return g ? external_pack_only(g, false) : amt_fail(AMT_ERR_INVALID_ARG, "null grid"); }
+extern "C" int amt_grid_halo_unpack(amt_grid *g) { return g ? external_pack_only(g, true) : amt_fail(AMT_ERR_INVALID_ARG, "null grid"); }
+
+// The planner: the message list of patch (ri, rj) of pi x pj from the shape alone.  Nothing of the device is touched.
+extern "C" int amt_halo_plan(int dtype_bytes, int periodic_x, int specified, int nested, int ids, int ide, int jds, int jde, int kde,
+                             int ims, int ime, int jms, int jme, int kms, int kme, int its, int ite, int jts, int jte, int kts, int kte,
+                             int ri, int rj, int pi, int pj, int flags, amt_halo_message *out, int cap, int *n)
+{
+    if (!n || cap < 0 || (cap > 0 && !out)) return amt_fail(AMT_ERR_INVALID_ARG, "amt_halo_plan: bad argument");
+    if (dtype_bytes != 4 && dtype_bytes != 8) return amt_fail(AMT_ERR_INVALID_ARG, "amt_halo_plan: dtype_bytes is 4 or 8");
+    if (ime < ims || jme < jms || kme < kms) return amt_fail(AMT_ERR_PRECONDITION, "amt_halo_plan: empty memory extents");
+    amt_domain d;
+    d.dtype_bytes = dtype_bytes; d.periodic_x = periodic_x; d.specified = specified; d.nested = nested;
+    d.ids = ids; d.ide = ide; d.jds = jds; d.jde = jde; d.kde = kde; d.ims = ims; d.ime = ime; d.jms = jms; d.jme = jme;
+    d.kms = kms; d.kme = kme; d.its = its; d.ite = ite; d.jts = jts; d.jte = jte; d.kts = kts; d.kte = kte;
+    amt_grid g;
+    const int rc = grid_topology(&g, &d, ri, rj, pi, pj, true, flags | AMT_SLAB_TRANSPORT_EXTERNAL, false, false);
+    if (rc) return rc;
+    amt_halo_message msg[4];
+    *n = halo_plan(&g, msg);
+    if (*n > cap) return amt_fail(AMT_ERR_INVALID_ARG, "amt_halo_plan: %d messages, room for %d", *n, cap);
+    for (int m = 0; m < *n; ++m) out[m] = msg[m];
+    return AMT_OK;
+}
+
 // ---------------------------------------------------------------------------
 // amt_slab_*: the pi = 1 case (rank = rj, world = pj); loopback loops j only
 // ---------------------------------------------------------------------------
@@ -563,6 +861,12 @@ extern "C" int amt_slab_destroy(amt_slab *s)
     delete s;
     return AMT_OK;
 }
+extern "C" int amt_slab_halo_messages(amt_slab *s, amt_halo_message *out, int cap, int *n) { return s ? external_messages(&s->g, out, cap, n) : amt_fail(AMT_ERR_INVALID_ARG, "null slab"); }
+extern "C" int amt_slab_step_begin(amt_slab *s) { return s ? external_begin(&s->g) : amt_fail(AMT_ERR_INVALID_ARG, "null slab"); }
+extern "C" int amt_slab_halo_wait(amt_slab *s) { return s ? external_wait(&s->g) : amt_fail(AMT_ERR_INVALID_ARG, "null slab"); }
+extern "C" int amt_slab_step_end(amt_slab *s) { return s ? external_end(&s->g) : amt_fail(AMT_ERR_INVALID_ARG, "null slab"); }
+extern "C" int amt_slab_halo_pack(amt_slab *s) { return s ? external_pack_only(&s->g, false) : amt_fail(AMT_ERR_INVALID_ARG, "null slab"); }
+extern "C" int amt_slab_halo_unpack(amt_slab *s) { return s ? external_pack_only(&s->g, true) : amt_fail(AMT_ERR_INVALID_ARG, "null slab"); }
 extern "C" int amt_slab_exchange(amt_slab *s) { return s ? grid_exchange_only(&s->g) : amt_fail(AMT_ERR_INVALID_ARG, "null slab"); }
 extern "C" int amt_slab_step(amt_slab *s, int n) { return s && n >= 0 ? grid_step(&s->g, n) : amt_fail(AMT_ERR_INVALID_ARG, "bad step argument"); }
 extern "C" int amt_slab_step_timed(amt_slab *s, int n, float *ms) { return s && n >= 0 ? grid_step_timed(&s->g, n, ms) : amt_fail(AMT_ERR_INVALID_ARG, "bad step argument"); }

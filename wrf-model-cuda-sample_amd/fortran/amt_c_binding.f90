@@ -27,7 +27,17 @@ MODULE amt_c_binding
    end type
    ! enum amt_slab_flags (amt_slab_create / amt_grid_create)
    integer(c_int), parameter :: AMT_SLAB_NO_OVERLAP = 1, AMT_SLAB_LOOPBACK = 2, AMT_SLAB_TRANSPORT_IPC = 4,  &
-                                AMT_SLAB_CYCLIC_X = 8, AMT_SLAB_CYCLIC_Y = 16
+                                AMT_SLAB_CYCLIC_X = 8, AMT_SLAB_CYCLIC_Y = 16,                                 &
+                                AMT_SLAB_TRANSPORT_EXTERNAL = 32, AMT_SLAB_EXTERNAL_HOST_BUFFERS = 64
+   ! one side's messages of a host-owned halo exchange (header section 11): the library owns the buffers, the host moves them
+   type, bind(C) :: amt_halo_message
+      integer(c_int) :: side, peer                           ! side: AMT_SIDE_* below, also the MPI tag
+      type(c_ptr) :: send
+      integer(c_size_t) :: send_bytes
+      type(c_ptr) :: recv
+      integer(c_size_t) :: recv_bytes
+      integer(c_int) :: on_host
+   end type
 
    interface
       ! (1) one-shot host drop-ins
@@ -359,6 +369,84 @@ MODULE amt_c_binding
          import :: c_ptr, c_int, c_double
          type(c_ptr), value :: grid
          real(c_double) :: x                                 ! in: this rank's value, out: the maximum
+         integer(c_int) :: rc
+      end function
+      ! (11) host-owned halo exchange (AMT_SLAB_TRANSPORT_EXTERNAL): per sweep step_begin, halo_wait, the host's sends and
+      !      receives (tag = side), step_end
+      function amt_grid_halo_messages(grid, out, cap, n) bind(C, name="amt_grid_halo_messages") result(rc)
+         import :: c_ptr, c_int, amt_halo_message
+         type(c_ptr), value :: grid
+         type(amt_halo_message) :: out(*)                    ! room for cap messages (at most 4)
+         integer(c_int), value :: cap
+         integer(c_int) :: n
+         integer(c_int) :: rc
+      end function
+      function amt_grid_step_begin(grid) bind(C, name="amt_grid_step_begin") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: grid
+         integer(c_int) :: rc
+      end function
+      function amt_grid_halo_wait(grid) bind(C, name="amt_grid_halo_wait") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: grid
+         integer(c_int) :: rc
+      end function
+      function amt_grid_step_end(grid) bind(C, name="amt_grid_step_end") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: grid
+         integer(c_int) :: rc
+      end function
+      function amt_grid_halo_pack(grid) bind(C, name="amt_grid_halo_pack") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: grid
+         integer(c_int) :: rc
+      end function
+      function amt_grid_halo_unpack(grid) bind(C, name="amt_grid_halo_unpack") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: grid
+         integer(c_int) :: rc
+      end function
+      function amt_slab_halo_messages(slab, out, cap, n) bind(C, name="amt_slab_halo_messages") result(rc)
+         import :: c_ptr, c_int, amt_halo_message
+         type(c_ptr), value :: slab
+         type(amt_halo_message) :: out(*)                    ! room for cap messages (at most 4)
+         integer(c_int), value :: cap
+         integer(c_int) :: n
+         integer(c_int) :: rc
+      end function
+      function amt_slab_step_begin(slab) bind(C, name="amt_slab_step_begin") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: slab
+         integer(c_int) :: rc
+      end function
+      function amt_slab_halo_wait(slab) bind(C, name="amt_slab_halo_wait") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: slab
+         integer(c_int) :: rc
+      end function
+      function amt_slab_step_end(slab) bind(C, name="amt_slab_step_end") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: slab
+         integer(c_int) :: rc
+      end function
+      function amt_slab_halo_pack(slab) bind(C, name="amt_slab_halo_pack") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: slab
+         integer(c_int) :: rc
+      end function
+      function amt_slab_halo_unpack(slab) bind(C, name="amt_slab_halo_unpack") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: slab
+         integer(c_int) :: rc
+      end function
+      function amt_halo_plan(dtype_bytes, periodic_x, specified, nested, ids, ide, jds, jde, kde, ims, ime, jms, jme,   &
+                             kms, kme, its, ite, jts, jte, kts, kte, ri, rj, pi, pj, flags, out, cap, n)             &
+                             bind(C, name="amt_halo_plan") result(rc)
+         import :: c_int, amt_halo_message
+         integer(c_int), value :: dtype_bytes, periodic_x, specified, nested, ids, ide, jds, jde, kde, ims, ime, jms, jme
+         integer(c_int), value :: kms, kme, its, ite, jts, jte, kts, kte, ri, rj, pi, pj, flags, cap
+         type(amt_halo_message) :: out(*)
+         integer(c_int) :: n
          integer(c_int) :: rc
       end function
 

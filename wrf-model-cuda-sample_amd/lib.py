@@ -54,6 +54,12 @@ class GuardReport(_Record):
                 ("member", ctypes.c_int32), ("offset", ctypes.c_int64), ("n_nonfinite", ctypes.c_int64)]
 
 
+class HaloMessage(_Record):
+    """``amt_halo_message`` (header section 11)"""
+    _fields_ = [("side", ctypes.c_int), ("peer", ctypes.c_int), ("send", ctypes.c_void_p), ("send_bytes", ctypes.c_size_t),
+                ("recv", ctypes.c_void_p), ("recv_bytes", ctypes.c_size_t), ("on_host", ctypes.c_int)]
+
+
 def library_path() -> Path:
     """The in-tree HIP library; AMT_LIBRARY overrides it (A/B builds of the kernels)."""
     import os
@@ -185,6 +191,19 @@ SYMBOLS = {
     "amt_ensemble_set_guard": (_I, [_P, _I]),
     "amt_domain_guard_report": (_I, [_P, ctypes.POINTER(GuardReport)]),
     "amt_ensemble_guard_report": (_I, [_P, ctypes.POINTER(GuardReport)]),
+    "amt_halo_plan": (_I, [_I] * (4 + 17 + 5) + [ctypes.POINTER(HaloMessage), _I, ctypes.POINTER(_I)]),
+    "amt_grid_halo_messages": (_I, [_P, ctypes.POINTER(HaloMessage), _I, ctypes.POINTER(_I)]),
+    "amt_slab_halo_messages": (_I, [_P, ctypes.POINTER(HaloMessage), _I, ctypes.POINTER(_I)]),
+    "amt_grid_step_begin": (_I, [_P]),
+    "amt_grid_halo_wait": (_I, [_P]),
+    "amt_grid_step_end": (_I, [_P]),
+    "amt_grid_halo_pack": (_I, [_P]),
+    "amt_grid_halo_unpack": (_I, [_P]),
+    "amt_slab_step_begin": (_I, [_P]),
+    "amt_slab_halo_wait": (_I, [_P]),
+    "amt_slab_step_end": (_I, [_P]),
+    "amt_slab_halo_pack": (_I, [_P]),
+    "amt_slab_halo_unpack": (_I, [_P]),
     "amt_march_force_shape": (_I, [_I] * 7),
     "amt_march_rows_for": (_I, [ctypes.c_long, _I, _I, ctypes.c_long, _I, _I]),
     "amt_march_set_xchunk": (_I, [_I]),

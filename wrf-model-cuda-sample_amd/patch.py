@@ -629,3 +629,202 @@ class NativeGridStepper:
             self.close()
         except Exception:
             pass
+
+
+# ---------------------------------------------------------------------------------------------
+# Host-owned halo exchange (include/amt_advance_mu_t.h section 11): the library packs one contiguous
+# message per side, the HOST moves the messages (MPI), the library unpacks.
+# ---------------------------------------------------------------------------------------------
+EXTERNAL_FLAG, HOST_BUFFERS_FLAG = 32, 64       # AMT_SLAB_TRANSPORT_EXTERNAL, AMT_SLAB_EXTERNAL_HOST_BUFFERS
+SIDE_ORDER = (_S.SIDE_BELOW, _S.SIDE_ABOVE, _S.SIDE_LEFT, _S.SIDE_RIGHT)      # the order of amt_grid_halo_messages
+OPPOSITE_SIDE = {_S.SIDE_BELOW: _S.SIDE_ABOVE, _S.SIDE_ABOVE: _S.SIDE_BELOW, _S.SIDE_LEFT: _S.SIDE_RIGHT, _S.SIDE_RIGHT: _S.SIDE_LEFT}
+
+
+def halo_layout(bounds, ri: int, rj: int, pi: int, pj: int, cyclic=(False, False)) -> dict:
+    """The statement of the message layout: ``{side: {"peer": rank, "send": runs, "recv": runs}}`` for every side of patch
+    (ri, rj) of pi x pj that has a neighbour, sides in SIDE_ORDER.  ``runs`` is a list of ``(field, index)``: the message is
+    the concatenation, in list order, of ``arrays[field][index]`` flattened in C order -- arrays in the (j, k, i) / (j, i)
+    memory layout, every memory level.  Rows: i fastest over ilo..ihi, then k.  Columns: k fastest, then j over jlo..jhi.
+    ilo..ihi, jlo..jhi: its..ite, jts..jte; in a cyclic direction the compute window's edges.  ``recv`` names the halo cells
+    the message is unpacked into (row jhi+1 / jlo-1, column ihi+1 / ilo-1): what a side sends is what the neighbour's
+    opposite side receives."""
+    b = bounds
+    left, right, below, above, _sends, _recvs = exchange_plan(ri, rj, pi, pj, cyclic)
+    c0, c1, r0, r1 = b.its - b.ims, b.ite - b.ims, b.jts - b.jms, b.jte - b.jms
+    w0, w1, v0, v1 = _edge_cells(b)
+    if cyclic[0]:
+        c0, c1 = w0, w1
+    if cyclic[1]:
+        r0, r1 = v0, v1
+    I, J = slice(c0, c1 + 1), slice(r0, r1 + 1)
+
+    def rows(names, r):
+        return [(n, (r, slice(None), I) if _S.field_rank(n) == 3 else (r, I)) for n in names]
+
+    def cols(names, c):
+        return [(n, (J, slice(None), c) if _S.field_rank(n) == 3 else (J, c)) for n in names]
+
+    out = {}
+    if below is not None:
+        out[_S.SIDE_BELOW] = dict(peer=below, send=rows(HALO_FROM_ABOVE, r0), recv=rows(HALO_FROM_BELOW, r0 - 1))
+    if above is not None:
+        out[_S.SIDE_ABOVE] = dict(peer=above, send=rows(HALO_FROM_BELOW, r1), recv=rows(HALO_FROM_ABOVE, r1 + 1))
+    if left is not None:
+        out[_S.SIDE_LEFT] = dict(peer=left, send=cols(HALO_FROM_RIGHT, c0), recv=cols(HALO_FROM_LEFT, c0 - 1))
+    if right is not None:
+        out[_S.SIDE_RIGHT] = dict(peer=right, send=cols(HALO_FROM_LEFT, c1), recv=cols(HALO_FROM_RIGHT, c1 + 1))
+    return out
+
+
+class _LibraryBytes:
+    """``nbytes`` of device memory the library owns at ``ptr``, for torch.as_tensor (as synth.NativeDomain.view); keeps the
+    stepper alive for as long as a tensor views the buffer."""
+
+    def __init__(self, owner, ptr: int, nbytes: int):
+        self.owner = owner
+        self.__cuda_array_interface__ = {"shape": (int(nbytes),), "typestr": "|u1", "data": (int(ptr), False), "version": 2, "strides": None}
+
+
+class HaloMessageView:
+    """One side's messages of an external stepper: ``side`` (synth.SIDE_*), ``peer`` (rank), ``send`` / ``recv`` as byte views
+    -- torch uint8 device tensors, or numpy uint8 arrays over page-locked host memory (``on_host``)."""
+
+    def __init__(self, side, peer, send, recv, on_host):
+        self.side, self.peer, self.send, self.recv, self.on_host = side, peer, send, recv, on_host
+
+
+class ExternalGridStepper:
+    """advance_mu_t on patch (ri, rj) of pi x pj with the HOST as the transport (``AMT_SLAB_TRANSPORT_EXTERNAL``): per sweep
+    ``begin()`` (pack + interior), ``halo_wait()``, the host copies every ``send`` into the matching ``recv`` of the peer (an
+    MPI host: Isend / Irecv with tag = side), ``end()`` (unpack + boundary cells).  Creation is not collective and needs no
+    communicator id; any number of steppers may share a process and a device.  ``host_buffers``: the messages lie in
+    page-locked host memory (an MPI that is not GPU-aware)."""
+
+    _HANDLE, _SLAB = "amt_grid", False
+
+    def __init__(self, patch: Patch, ri: int, rj: int, pi: int, pj: int, *, cyclic=(False, False), overlap: bool = True,
+                 host_buffers: bool = False, stream=None, variant: int = 0):
+        import ctypes
+        import torch
+        from . import lib as _lib
+        from .synth import FIELD_NAMES
+        self._lib, self._ct = _lib, ctypes
+        self.L = L = _lib.load_library()
+        self.patch, self.ri, self.rj, self.pi, self.pj = patch, ri, rj, pi, pj
+        self.rank = rj * pi + ri
+        self.cyclic = (bool(cyclic[0]), bool(cyclic[1]))
+        self.host_buffers = bool(host_buffers)
+        self._halo_sides = cyclic_sides(ri, rj, pi, pj, self.cyclic)
+        t0 = patch.arrays["t_1"]
+        if not t0.is_cuda:
+            raise TypeError(f"{type(self).__name__} needs a device patch (there is no CPU path)")
+        b = patch.bounds
+        for name in FIELD_NAMES:
+            t = patch.arrays[name]
+            if not (t.is_cuda and t.dtype == t0.dtype and t.is_contiguous() and tuple(t.shape) == tuple(b.shape(name))):
+                raise TypeError(f"{name}: need a contiguous device tensor of shape {b.shape(name)}")
+        self.stream = stream if stream is not None else torch.cuda.Stream(device=t0.device)
+        self.device_index = t0.device.index if t0.device.index is not None else torch.cuda.current_device()
+        fields = (ctypes.c_void_p * len(FIELD_NAMES))(*[patch.arrays[n].data_ptr() for n in FIELD_NAMES])
+        self._dom, self._h = ctypes.c_void_p(), ctypes.c_void_p()
+        self._messages = None
+        with torch.cuda.device(self.device_index):
+            _lib.check(L.amt_domain_wrap(ctypes.byref(self._dom), t0.element_size(), *patch.config.as_ints(),
+                                         *b.as_tuple(), fields, ctypes.c_void_p(self.stream.cuda_stream)))
+            try:
+                _lib.check(L.amt_domain_set_scalars(self._dom, patch.rdx, patch.rdy, patch.dts, patch.epssm))
+                _lib.check(L.amt_domain_set_variant(self._dom, int(variant)))
+                self.flags = (EXTERNAL_FLAG | (0 if overlap else 1) | (HOST_BUFFERS_FLAG if host_buffers else 0)
+                              | (CYCLIC_X_FLAG if self.cyclic[0] else 0) | (CYCLIC_Y_FLAG if self.cyclic[1] else 0))
+                if self._SLAB:
+                    _lib.check(L.amt_slab_create(ctypes.byref(self._h), self._dom, rj, pj, None, self.flags))
+                else:
+                    _lib.check(L.amt_grid_create(ctypes.byref(self._h), self._dom, ri, rj, pi, pj, None, self.flags))
+            except BaseException:
+                L.amt_domain_destroy(self._dom)
+                self._dom = ctypes.c_void_p()
+                raise
+
+    def _dev(self):
+        import torch
+        return torch.cuda.device(self.device_index)
+
+    def _call(self, name: str):
+        with self._dev():
+            self._lib.check(getattr(self.L, f"{self._HANDLE}_{name}")(self._h))
+
+    def begin(self):
+        """Asynchronous: [self-wrap refresh,] pack, then the interior cells (all of it with ``overlap=False``: nothing)."""
+        self._call("step_begin")
+
+    def halo_wait(self):
+        """Host wait: this sweep's ``send`` buffers are readable and the ``recv`` buffers may be overwritten."""
+        self._call("halo_wait")
+
+    def end(self):
+        """Asynchronous; every ``recv`` holds this sweep's message: unpack, then the boundary rows and columns."""
+        self._call("step_end")
+
+    def halo_pack(self):
+        self._call("halo_pack")
+
+    def halo_unpack(self):
+        self._call("halo_unpack")
+
+    def sync(self):
+        self._call("sync")
+
+    def messages(self):
+        """The handle's messages (``HaloMessageView``), sides in SIDE_ORDER; made once, the views stay valid until close()."""
+        if self._messages is None:
+            import numpy as np
+            import torch
+            ct = self._ct
+            raw, n = (self._lib.HaloMessage * 4)(), ct.c_int()
+            self._lib.check(getattr(self.L, f"{self._HANDLE}_halo_messages")(self._h, raw, 4, ct.byref(n)))
+
+            def view(ptr, nbytes, on_host):
+                if on_host:
+                    return np.frombuffer((ct.c_ubyte * nbytes).from_address(ptr), dtype=np.uint8)
+                return torch.as_tensor(_LibraryBytes(self, ptr, nbytes), device=torch.device("cuda", self.device_index))
+
+            with self._dev():
+                self._messages = [HaloMessageView(m.side, m.peer, view(m.send, m.send_bytes, m.on_host),
+                                                  view(m.recv, m.recv_bytes, m.on_host), bool(m.on_host)) for m in raw[:n.value]]
+        return self._messages
+
+    def next_substep_inputs(self, seed: int, sweep: int, poison: bool = True):
+        """As NativeGridStepper.next_substep_inputs: new values in the exchanged fields, NaN in the halo rows and columns."""
+        _substep_inputs(self, self._dom, seed, sweep, self._halo_sides if poison else 0)
+
+    def halo_bytes_per_sweep(self) -> int:
+        return int(getattr(self.L, f"{self._HANDLE}_halo_bytes")(self._h))
+
+    def transport(self) -> str:
+        """'external', or 'none' for a patch without a neighbour."""
+        return getattr(self.L, f"{self._HANDLE}_transport")(self._h).decode()
+
+    def close(self):
+        self._messages = None
+        if self._h:
+            with self._dev():
+                getattr(self.L, f"{self._HANDLE}_destroy")(self._h)
+            self._h = self._ct.c_void_p()
+        if self._dom:
+            self.L.amt_domain_destroy(self._dom)
+            self._dom = self._ct.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ExternalSlabStepper(ExternalGridStepper):
+    """The pi = 1 case through ``amt_slab_*``: j-slab ``rank`` of ``world``."""
+
+    _HANDLE, _SLAB = "amt_slab", True
+
+    def __init__(self, patch: Patch, rank: int, world: int, **kw):
+        super().__init__(patch, 0, rank, 1, world, **kw)
