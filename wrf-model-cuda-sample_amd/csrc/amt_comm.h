@@ -50,15 +50,3 @@ void amt_exchange_set_skew_us(AmtExchange *x, int microseconds);    // test hook
 bool amt_exchange_owns_skew(const AmtExchange *x);
 const char *amt_exchange_pull_mode(const AmtExchange *x);             // "fused kernel" / "copy engine" / "" (RCCL)
 bool amt_exchange_active(const AmtExchange *x);       // false: no segment at all (a world of one without loopback)
-
-// The host-owned exchange (AMT_SLAB_TRANSPORT_EXTERNAL, amt_halo.hip): no AmtExchange at all.  One launch moves up to
-// AMT_HALO_MAX_JOBS jobs between the patch's arrays and its dense messages: job q is `runs` runs of `len` elements, run r at
-// array + r * idim elements and at msg + r * len; scatter = false packs (array -> message), true unpacks.
-enum { AMT_HALO_MAX_JOBS = 12 };          // 5 + 1 row fields and 5 + 1 column fields
-struct AmtHaloJob {
-    void *array;
-    void *msg;
-    long runs;
-    int len;
-};
-int amt_halo_launch(hipStream_t stream, int dtype_bytes, bool scatter, long idim, const AmtHaloJob *jobs, int n);

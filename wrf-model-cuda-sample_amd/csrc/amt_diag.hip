@@ -6,7 +6,7 @@
 // workgroup of 256 threads is 2^s lanes along i times 256 / 2^s runs (s: the smallest power of two that covers a run's chunks,
 // at most 256 lanes), and the workgroups stride over the groups of runs.  Which thread takes which element therefore depends on
 // the BOX SHAPE ALONE -- not on where the array lies.  Alignment only decides how a chunk is loaded, per run as in
-// amt_cyclic_kernel: a run whose first element lies on a 16-byte boundary moves its whole chunks as 16-byte loads; the last,
+// amt_halo_kernel: a run whose first element lies on a 16-byte boundary moves its whole chunks as 16-byte loads; the last,
 // partial chunk of a run and every chunk of a run that starts off a boundary are single-element loads.  No load touches an
 // element outside the box, so nothing outside the array is read and a NaN in a halo cell cannot reach a result.
 //

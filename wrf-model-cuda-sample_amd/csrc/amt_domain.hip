@@ -1,6 +1,6 @@
 // amt_domain.hip -- the resident domain handle amt_domain_*: native owner of the 26 device arrays,
 // a stream and the scalars, for C / Fortran hosts that keep the state on the GPU across sub-steps.
-#include "amt_internal.h"
+#include "amt_halo.h"
 #include <fcntl.h>
 #include <sys/file.h>
 #include <time.h>
@@ -278,27 +278,23 @@ int amt_domain_poison_t(amt_domain *d, int sides, W nan)
     const long idim = d->ime - d->ims + 1, kdim = d->kme - d->kms + 1, jdim = d->jme - d->jms + 1;
     AmtPoisonJobs<W> jobs{};
     jobs.nan = nan;
-    auto row = [&](int f, int j) {
-        const long n = amt_field_rank(f) == 3 ? idim * kdim : idim;
-        const int q = jobs.n++;
-        jobs.base[q] = static_cast<W *>(d->field[f]) + (long)(j - d->jms) * n;
-        jobs.count[q] = n;
-        jobs.stride[q] = 1;
-    };
-    auto column = [&](int f, int i) {
-        const int q = jobs.n++;
-        jobs.base[q] = static_cast<W *>(d->field[f]) + (i - d->ims);
-        jobs.count[q] = amt_field_rank(f) == 3 ? kdim * jdim : jdim;
-        jobs.stride[q] = idim;
-    };
     if ((sides & (AMT_SIDE_BELOW | AMT_SIDE_ABOVE)) && (d->jts - 1 < d->jms || d->jte + 1 > d->jme))
         return amt_fail(AMT_ERR_PRECONDITION, "amt_domain_poison_halos: the patch holds no halo row below jts / above jte");
     if ((sides & (AMT_SIDE_LEFT | AMT_SIDE_RIGHT)) && (d->its - 1 < d->ims || d->ite + 1 > d->ime))
         return amt_fail(AMT_ERR_PRECONDITION, "amt_domain_poison_halos: the patch holds no halo column left of its / right of ite");
-    if (sides & AMT_SIDE_ABOVE) for (int f : {AMT_F_V, AMT_F_V_1, AMT_F_T_1, AMT_F_MUV, AMT_F_MSFVX_INV}) row(f, d->jte + 1);
-    if (sides & AMT_SIDE_BELOW) row(AMT_F_T_1, d->jts - 1);
-    if (sides & AMT_SIDE_RIGHT) for (int f : {AMT_F_U, AMT_F_U_1, AMT_F_T_1, AMT_F_MUU, AMT_F_MSFUY}) column(f, d->ite + 1);
-    if (sides & AMT_SIDE_LEFT) column(AMT_F_T_1, d->its - 1);
+    // the halo cells of amt_halo.h's table: a whole memory row jts-1 / jte+1, a whole memory column its-1 / ite+1
+    const int cell[AMT_HALO_SIDES] = {d->jts - 1, d->jte + 1, d->its - 1, d->ite + 1};
+    for (int side = 0; side < AMT_HALO_SIDES; ++side) {
+        if (!(sides & (1 << side))) continue;
+        const bool column = amt_halo_is_column(side);
+        for (int k = 0; k < amt_halo_recv(side).n; ++k) {
+            const int f = amt_halo_recv(side).field[k], q = jobs.n++;
+            const long levels = amt_halo_levels(f, kdim);
+            jobs.base[q] = static_cast<W *>(d->field[f]) + (column ? amt_halo_at(*d, f, cell[side], d->jms) : amt_halo_at(*d, f, d->ims, cell[side]));
+            jobs.count[q] = levels * (column ? jdim : idim);
+            jobs.stride[q] = column ? idim : 1;
+        }
+    }
     if (jobs.n == 0) return AMT_OK;
     long most = 0;
     for (int q = 0; q < jobs.n; ++q) most = jobs.count[q] > most ? jobs.count[q] : most;

@@ -3,15 +3,13 @@
 // (section 5; the reference splits j over its GPUs inside one process with host-sourced halos,
 // advance_mu_t_no_async.cu:108-162).
 //
-// What crosses a patch boundary (the stencil reads (i+-1, j) and (i, j+-1) only: no diagonal neighbours):
-//   from above  (j+1): row jte+1 of v, v_1, t_1, muv, msfvx_inv      module_small_step_em.f90:143-144, :241
-//   from below  (j-1): row jts-1 of t_1                               :242
-//   from right  (i+1): column ite+1 of u, u_1, t_1, muu, msfuy        :145-146, :244
-//   from left   (i-1): column its-1 of t_1                            :245
+// What crosses a patch boundary is amt_halo.h's table (the stencil reads (i+-1, j) and (i, j+-1) only: no diagonal neighbours).
 // A j row of the (i,k,j) layout is one contiguous run and travels in place.  A column is kdim*jdim elements at stride idim:
-// one HIP kernel gathers the columns a patch sends into two contiguous buffers (one per direction), the buffers travel like
-// rows, one kernel scatters what arrived into the halo columns.  The exchange engine of amt_comm.h carries both.
+// one launch of the mover (amt_halo.hip) gathers the columns a patch sends into two contiguous buffers (one per direction), the
+// buffers travel like rows, one launch scatters what arrived into the halo columns.  The exchange engine of amt_comm.h carries
+// both.
 #include "amt_comm.h"
+#include "amt_halo.h"
 #include <vector>
 
 struct amt_grid {
@@ -26,7 +24,7 @@ struct amt_grid {
     hipEvent_t inputs_final = nullptr, edges_done = nullptr, t0 = nullptr, t1 = nullptr;
     // Cyclic boundaries (AMT_SLAB_CYCLIC_X / _Y).  wrap_*: the direction has several ranks and the edge
     // ranks are each other's neighbours (the wrap columns / rows travel as ordinary segments); self_wrap: amt_cyclic_axes of
-    // the directions with ONE rank, refreshed by amt_cyclic_kernel on the domain's stream in front of every sweep.
+    // the directions with ONE rank, refreshed by amt_halo_kernel on the domain's stream in front of every sweep.
     bool wrap_x = false, wrap_y = false;
     int self_wrap = 0;
     int skew_us = 0;                                        // test hook: the neighbours' rows arrive this late
@@ -48,37 +46,6 @@ struct amt_slab {
 };
 
 namespace {
-const int kRowsFromAbove[] = {AMT_F_V, AMT_F_V_1, AMT_F_T_1, AMT_F_MUV, AMT_F_MSFVX_INV};
-const int kRowsFromBelow[] = {AMT_F_T_1};
-const int kColsFromRight[] = {AMT_F_U, AMT_F_U_1, AMT_F_T_1, AMT_F_MUU, AMT_F_MSFUY};       // 3-D ones first
-const int kColsFromLeft[] = {AMT_F_T_1};
-
-// One launch gathers (scatter = 0) or scatters (1) up to six columns: job q moves the `count` elements of memory column `col`
-// of an array with rows of `idim` elements -- element e of the column is array[e * idim + col] -- from / to the contiguous run
-// `packed`.  Lanes run along e (levels and rows): the packed side is coalesced, the array side touches one line per element,
-// which is what a column is.
-template <typename W>
-struct AmtColumnJobs {
-    W *array[6];
-    W *packed[6];
-    long col[6];
-    long count[6];
-    long idim;
-    int n, scatter;
-};
-template <typename W>
-__global__ __launch_bounds__(256) void amt_grid_columns(AmtColumnJobs<W> jobs)
-{
-    const int q = blockIdx.y;
-    W *array = jobs.array[q] + jobs.col[q];
-    W *packed = jobs.packed[q];
-    const long n = jobs.count[q];
-    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
-        if (jobs.scatter) array[e * jobs.idim] = packed[e];
-        else packed[e] = array[e * jobs.idim];
-    }
-}
-
 // First / last column and row a patch sends and the halo cells it receives into.  Without a cyclic flag: its, ite, jts, jte as
 // ever.  With one, the compute window's edges (amt_compute_window) instead: the last patch of a periodic direction may end at
 // ide-1 or at ide (jde-1 or jde), and what its neighbour across the domain edge reads is column ide-1 / row jde-1, what it
@@ -94,61 +61,59 @@ EdgeCells edge_cells(const amt_grid *g)
     return e;
 }
 
-struct ColumnPlan {
-    size_t rows3, rows2, es;
-    size_t bytes_from_right() const { return (3 * rows3 + 2 * rows2) * es; }      // u, u_1, t_1, muu, msfuy
-    size_t bytes_from_left() const { return rows3 * es; }                          // t_1
+// Appends the jobs between the arrays and ONE dense run of memory `packed` (a column buffer, a message): for every field of
+// `list`, one behind the other, `per_level` runs per memory level of `len` elements each, from element (i, kms, j) on.
+//   a row:  per_level = 1, len = its columns;    columns: per_level = their rows, len = 1
+struct HaloJobs {
+    AmtHaloJob job[AMT_HALO_MAX_JOBS];
+    int n = 0;
 };
-ColumnPlan column_plan(const amt_domain *d)
+void halo_jobs(HaloJobs &out, const amt_domain *d, const AmtHaloFields &list, int i, int j, long per_level, int len, void *packed, bool scatter)
 {
-    const size_t kdim = d->kme - d->kms + 1, jdim = d->jme - d->jms + 1;
-    return ColumnPlan{kdim * jdim, jdim, (size_t)d->dtype_bytes};
+    const long idim = d->ime - d->ims + 1, kdim = d->kme - d->kms + 1;
+    const size_t es = (size_t)d->dtype_bytes;
+    char *p = static_cast<char *>(packed);
+    for (int q = 0; q < list.n; ++q) {
+        const int f = list.field[q];
+        char *a = static_cast<char *>(d->field[f]) + (size_t)amt_halo_at(*d, f, i, j) * es;
+        const long runs = amt_halo_levels(f, kdim) * per_level;
+        out.job[out.n++] = scatter ? AmtHaloJob{p, a, runs, len, len, idim, 0} : AmtHaloJob{a, p, runs, len, idim, len, 0};
+        p += (size_t)(runs * len) * es;
+    }
 }
 
-template <typename W>
+// bytes of the packed whole memory columns (every level, every memory row) received from `side`
+size_t column_bytes(const amt_domain *d, int side)
+{
+    return (size_t)amt_halo_elems(side, d->kme - d->kms + 1) * (size_t)(d->jme - d->jms + 1) * (size_t)d->dtype_bytes;
+}
+
+// One launch gathers the columns the patch sends into to_left / to_right (scatter = false) or scatters from_right / from_left
+// into its halo columns (true).
 int grid_columns(amt_grid *g, hipStream_t stream, bool scatter)
 {
     amt_domain *d = g->dom;
-    const ColumnPlan cp = column_plan(d);
-    AmtColumnJobs<W> jobs{};
-    jobs.idim = d->ime - d->ims + 1;
-    jobs.scatter = scatter ? 1 : 0;
-    auto add = [&](int field, long col, void *packed, size_t offset_elems) {
-        const int q = jobs.n++;
-        jobs.array[q] = static_cast<W *>(d->field[field]);
-        jobs.col[q] = col;
-        jobs.count[q] = (long)(amt_field_rank(field) == 3 ? cp.rows3 : cp.rows2);
-        jobs.packed[q] = static_cast<W *>(packed) + offset_elems;
-    };
     const EdgeCells ec = edge_cells(g);
-    const long c_first = ec.ilo - d->ims, c_last = ec.ihi - d->ims;
-    const int side_a = scatter ? g->right : g->left;      // gather: what the LEFT neighbour needs; scatter: what came from the RIGHT
-    const int side_b = scatter ? g->left : g->right;
-    if (side_a >= 0) {
-        size_t off = 0;
-        for (int f : kColsFromRight) {
-            add(f, scatter ? c_last + 1 : c_first, scatter ? g->from_right : g->to_left, off);
-            off += amt_field_rank(f) == 3 ? cp.rows3 : cp.rows2;
-        }
+    const long jdim = d->jme - d->jms + 1;
+    HaloJobs jobs;
+    if (scatter) {
+        if (g->right >= 0) halo_jobs(jobs, d, amt_halo_recv(AMT_HALO_RIGHT), ec.ihi + 1, d->jms, jdim, 1, g->from_right, true);
+        if (g->left >= 0) halo_jobs(jobs, d, amt_halo_recv(AMT_HALO_LEFT), ec.ilo - 1, d->jms, jdim, 1, g->from_left, true);
+    } else {
+        if (g->left >= 0) halo_jobs(jobs, d, amt_halo_sent(AMT_HALO_LEFT), ec.ilo, d->jms, jdim, 1, g->to_left, false);
+        if (g->right >= 0) halo_jobs(jobs, d, amt_halo_sent(AMT_HALO_RIGHT), ec.ihi, d->jms, jdim, 1, g->to_right, false);
     }
-    if (side_b >= 0)
-        for (int f : kColsFromLeft) add(f, scatter ? c_first - 1 : c_last, scatter ? g->from_left : g->to_right, 0);
-    if (jobs.n == 0) return AMT_OK;
-    long blocks = ((long)cp.rows3 + 255) / 256;
-    if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(amt_grid_columns<W>, dim3((unsigned)blocks, (unsigned)jobs.n), dim3(256), 0, stream, jobs);
-    AMT_HIP(hipGetLastError());
-    return AMT_OK;
+    return amt_halo_launch(stream, d->dtype_bytes, 1, jobs.job, jobs.n);
 }
 int grid_pack(amt_grid *g, hipStream_t s)
 {
     if (amt_test_fault("skip_pack", ++g->packs)) return AMT_OK;
-    return g->dom->dtype_bytes == 8 ? grid_columns<uint64_t>(g, s, false) : grid_columns<uint32_t>(g, s, false);
+    return grid_columns(g, s, false);
 }
 int grid_unpack(amt_grid *g, hipStream_t s)
 {
     if (amt_test_fault("skip_unpack", g->packs)) return AMT_OK;
-    return g->dom->dtype_bytes == 8 ? grid_columns<uint64_t>(g, s, true) : grid_columns<uint32_t>(g, s, true);
+    return grid_columns(g, s, true);
 }
 
 // Test hook (amt_*_set_skew_us, RCCL transport): holds the communication stream for `ticks` of the 100 MHz real-time counter, so
@@ -412,20 +377,16 @@ int halo_plan(const amt_grid *g, amt_halo_message out[4])
 {
     const amt_domain *d = g->dom;
     const EdgeCells ec = edge_cells(g);
-    const size_t kdim = d->kme - d->kms + 1, es = (size_t)d->dtype_bytes;
+    const long kdim = d->kme - d->kms + 1;
     const size_t ni = ec.ihi >= ec.ilo ? ec.ihi - ec.ilo + 1 : 0, nj = ec.jhi >= ec.jlo ? ec.jhi - ec.jlo + 1 : 0;
-    const size_t five_rows = (3 * kdim + 2) * ni * es, one_row = kdim * ni * es;        // v, v_1, t_1, muv, msfvx_inv / t_1
-    const size_t five_cols = (3 * kdim + 2) * nj * es, one_col = kdim * nj * es;        // u, u_1, t_1, muu, msfuy / t_1
+    const int peer[AMT_HALO_SIDES] = {g->below, g->above, g->left, g->right};
     int n = 0;
-    auto add = [&](int side, int peer, size_t send, size_t recv) {
-        if (peer < 0) return;
-        out[n] = amt_halo_message{side, peer, nullptr, send, nullptr, recv, g->host_buffers ? 1 : 0};
-        ++n;
-    };
-    add(AMT_SIDE_BELOW, g->below, five_rows, one_row);
-    add(AMT_SIDE_ABOVE, g->above, one_row, five_rows);
-    add(AMT_SIDE_LEFT, g->left, five_cols, one_col);
-    add(AMT_SIDE_RIGHT, g->right, one_col, five_cols);
+    for (int side = 0; side < AMT_HALO_SIDES; ++side) {
+        if (peer[side] < 0) continue;
+        const size_t edge_bytes = (amt_halo_is_column(side) ? nj : ni) * (size_t)d->dtype_bytes;
+        out[n++] = amt_halo_message{1 << side, peer[side], nullptr, (size_t)amt_halo_elems(side ^ 1, kdim) * edge_bytes, nullptr,
+                                    (size_t)amt_halo_elems(side, kdim) * edge_bytes, g->host_buffers ? 1 : 0};
+    }
     return n;
 }
 
@@ -456,51 +417,20 @@ int external_move(amt_grid *g, hipStream_t stream, bool scatter)
 {
     amt_domain *d = g->dom;
     const EdgeCells ec = edge_cells(g);
-    const long idim = d->ime - d->ims + 1, kdim = d->kme - d->kms + 1;
     const long ni = ec.ihi - ec.ilo + 1, nj = ec.jhi - ec.jlo + 1;
     if (ni < 1 || nj < 1) return AMT_OK;
-    const size_t es = (size_t)d->dtype_bytes;
-    AmtHaloJob jobs[AMT_HALO_MAX_JOBS];
-    int n = 0;
-    // element (i, kms, j) of a 3-D field / (i, j) of a 2-D one
-    auto at = [&](int f, int i, int j) {
-        const long off = ((long)(j - d->jms) * (amt_field_rank(f) == 3 ? kdim : 1)) * idim + (i - d->ims);
-        return static_cast<char *>(d->field[f]) + (size_t)off * es;
-    };
-    auto rows = [&](const int *fields, int count, int j, void *msg) {
-        char *m = static_cast<char *>(msg);
-        for (int q = 0; q < count; ++q) {
-            const long runs = amt_field_rank(fields[q]) == 3 ? kdim : 1;
-            jobs[n++] = AmtHaloJob{at(fields[q], ec.ilo, j), m, runs, (int)ni};
-            m += (size_t)(runs * ni) * es;
-        }
-    };
-    auto cols = [&](const int *fields, int count, int i, void *msg) {
-        char *m = static_cast<char *>(msg);
-        for (int q = 0; q < count; ++q) {
-            const long runs = (amt_field_rank(fields[q]) == 3 ? kdim : 1) * nj;
-            jobs[n++] = AmtHaloJob{at(fields[q], i, ec.jlo), m, runs, 1};
-            m += (size_t)runs * es;
-        }
-    };
+    // per side: the edge cell the patch sends, the halo cell it receives into
+    const int sent[AMT_HALO_SIDES] = {ec.jlo, ec.jhi, ec.ilo, ec.ihi}, halo[AMT_HALO_SIDES] = {ec.jlo - 1, ec.jhi + 1, ec.ilo - 1, ec.ihi + 1};
+    HaloJobs jobs;
     for (int k = 0; k < g->n_msg; ++k) {
         const amt_halo_message &m = g->msg[k];
-        switch (m.side) {
-        case AMT_SIDE_BELOW:
-            if (scatter) rows(kRowsFromBelow, 1, ec.jlo - 1, m.recv); else rows(kRowsFromAbove, 5, ec.jlo, m.send);
-            break;
-        case AMT_SIDE_ABOVE:
-            if (scatter) rows(kRowsFromAbove, 5, ec.jhi + 1, m.recv); else rows(kRowsFromBelow, 1, ec.jhi, m.send);
-            break;
-        case AMT_SIDE_LEFT:
-            if (scatter) cols(kColsFromLeft, 1, ec.ilo - 1, m.recv); else cols(kColsFromRight, 5, ec.ilo, m.send);
-            break;
-        default:
-            if (scatter) cols(kColsFromRight, 5, ec.ihi + 1, m.recv); else cols(kColsFromLeft, 1, ec.ihi, m.send);
-            break;
-        }
+        const int side = amt_halo_side_index(m.side), cell = scatter ? halo[side] : sent[side];
+        const AmtHaloFields &list = scatter ? amt_halo_recv(side) : amt_halo_sent(side);
+        void *msg = scatter ? m.recv : m.send;
+        if (amt_halo_is_column(side)) halo_jobs(jobs, d, list, cell, ec.jlo, nj, 1, msg, scatter);
+        else halo_jobs(jobs, d, list, ec.ilo, cell, 1, (int)ni, msg, scatter);
     }
-    return amt_halo_launch(stream, d->dtype_bytes, scatter, idim, jobs, n);
+    return amt_halo_launch(stream, d->dtype_bytes, 1, jobs.job, jobs.n);
 }
 
 int external_only(const amt_grid *g, const char *who)
@@ -663,27 +593,30 @@ int grid_setup(amt_grid *g, amt_domain *dom, int ri, int rj, int pi, int pj, con
         if (e != hipSuccess) return amt_fail(AMT_ERR_HIP, "amt_grid_create: %s", hipGetErrorString(e));
         return external_buffers(g);
     }
-    const ColumnPlan cp = column_plan(dom);
-    if (e == hipSuccess && g->left >= 0) e = hipMalloc(&g->to_left, cp.bytes_from_right());
-    if (e == hipSuccess && g->right >= 0) e = hipMalloc(&g->from_right, cp.bytes_from_right());
-    if (e == hipSuccess && g->right >= 0) e = hipMalloc(&g->to_right, cp.bytes_from_left());
-    if (e == hipSuccess && g->left >= 0) e = hipMalloc(&g->from_left, cp.bytes_from_left());
+    const size_t from_right = column_bytes(dom, AMT_HALO_RIGHT), from_left = column_bytes(dom, AMT_HALO_LEFT);
+    if (e == hipSuccess && g->left >= 0) e = hipMalloc(&g->to_left, from_right);         // what my left neighbour receives from its right
+    if (e == hipSuccess && g->right >= 0) e = hipMalloc(&g->from_right, from_right);
+    if (e == hipSuccess && g->right >= 0) e = hipMalloc(&g->to_right, from_left);
+    if (e == hipSuccess && g->left >= 0) e = hipMalloc(&g->from_left, from_left);
     if (e != hipSuccess) return amt_fail(e == hipErrorOutOfMemory ? AMT_ERR_ALLOC : AMT_ERR_HIP, "amt_grid_create: %s", hipGetErrorString(e));
     // the segments of one exchange.  Per pair of ranks the order of the sends is the order of the receives on the other side.
-    const size_t idim = dom->ime - dom->ims + 1, kdim = dom->kme - dom->kms + 1;
-    auto row = [&](int f, int j, int peer) {
-        const size_t count = amt_field_rank(f) == 3 ? idim * kdim : idim;
-        return AmtSeg{static_cast<char *>(dom->field[f]) + (size_t)(j - dom->jms) * count * dom->dtype_bytes, count * dom->dtype_bytes, peer};
-    };
+    const size_t es = (size_t)dom->dtype_bytes, idim = dom->ime - dom->ims + 1, kdim = dom->kme - dom->kms + 1;
     std::vector<AmtSeg> sends, recvs;
-    if (g->below >= 0) for (int f : kRowsFromAbove) sends.push_back(row(f, ec.jlo, g->below));
-    if (g->above >= 0) for (int f : kRowsFromBelow) sends.push_back(row(f, ec.jhi, g->above));
-    if (g->left >= 0) sends.push_back(AmtSeg{g->to_left, cp.bytes_from_right(), g->left});
-    if (g->right >= 0) sends.push_back(AmtSeg{g->to_right, cp.bytes_from_left(), g->right});
-    if (g->above >= 0) for (int f : kRowsFromAbove) recvs.push_back(row(f, ec.jhi + 1, g->above));
-    if (g->below >= 0) for (int f : kRowsFromBelow) recvs.push_back(row(f, ec.jlo - 1, g->below));
-    if (g->right >= 0) recvs.push_back(AmtSeg{g->from_right, cp.bytes_from_right(), g->right});
-    if (g->left >= 0) recvs.push_back(AmtSeg{g->from_left, cp.bytes_from_left(), g->left});
+    auto rows = [&](std::vector<AmtSeg> &segs, const AmtHaloFields &list, int j, int peer) {       // whole memory rows j, in place
+        for (int q = 0; q < list.n; ++q) {
+            const int f = list.field[q];
+            segs.push_back(AmtSeg{static_cast<char *>(dom->field[f]) + (size_t)amt_halo_at(*dom, f, dom->ims, j) * es,
+                                  (size_t)amt_halo_levels(f, kdim) * idim * es, peer});
+        }
+    };
+    if (g->below >= 0) rows(sends, amt_halo_sent(AMT_HALO_BELOW), ec.jlo, g->below);
+    if (g->above >= 0) rows(sends, amt_halo_sent(AMT_HALO_ABOVE), ec.jhi, g->above);
+    if (g->left >= 0) sends.push_back(AmtSeg{g->to_left, from_right, g->left});
+    if (g->right >= 0) sends.push_back(AmtSeg{g->to_right, from_left, g->right});
+    if (g->above >= 0) rows(recvs, amt_halo_recv(AMT_HALO_ABOVE), ec.jhi + 1, g->above);
+    if (g->below >= 0) rows(recvs, amt_halo_recv(AMT_HALO_BELOW), ec.jlo - 1, g->below);
+    if (g->right >= 0) recvs.push_back(AmtSeg{g->from_right, from_right, g->right});
+    if (g->left >= 0) recvs.push_back(AmtSeg{g->from_left, from_left, g->left});
     return amt_exchange_create(&g->xchg, transport, rank, world, unique_id, dom->device, sends.data(), (int)sends.size(),
                                recvs.data(), (int)recvs.size(), loop_i || loop_j);
 }
