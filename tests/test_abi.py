@@ -41,6 +41,26 @@ def test_headers_are_plain_c99(tmp_path):
     assert r.returncode == 0, r.stderr
 
 
+def test_field_table_and_kept_arrays_follow_the_enum(pkg):
+    """csrc/amt_internal.h's field table has a row for every AMT_F_* in the enum's order, the names are synth.FIELD_NAMES, and
+    the one-shot call's kept-array table names 17 cached inputs, then exactly the 7 fields with `out` (a source-level check)."""
+    csrc = ROOT / "wrf-model-cuda-sample_amd" / "csrc"
+    enum = re.search(r"enum amt_field \{(.*?)AMT_F_COUNT", (ROOT / "include" / "amt_synth.h").read_text(), re.S).group(1)
+    ids = re.findall(r"AMT_F_([A-Z0-9_]+)", enum)
+    rows = re.findall(r"\bX\((\w+), (\w+), ([01]), ([01])\)", (csrc / "amt_internal.h").read_text())
+    assert [r[0] for r in rows] == ids and len(ids) == 26
+    assert tuple(r[1] for r in rows) == tuple(pkg.synth.FIELD_NAMES)
+    assert [r[1].upper() for r in rows] == ids                    # a field's name is its id in lower case
+    out = {r[0] for r in rows if r[3] == "1"}
+    assert out == {n.upper() for n in pkg.synth.OUTPUTS}
+    assert all(r[2] == "1" or r[3] == "1" for r in rows)          # nothing is neither read nor assigned
+    oneshot = (csrc / "amt_oneshot.hip").read_text()
+    kept = re.findall(r"AMT_F_([A-Z0-9_]+)", re.search(r"kKeepField\[\] = \{(.*?)\};", oneshot, re.S).group(1))
+    ncache = int(re.search(r"constexpr int NCACHE = (\d+);", oneshot).group(1))
+    assert ncache == 17 and len(kept) == 24 and len(set(kept)) == 24 and set(kept) <= set(ids)
+    assert set(kept[ncache:]) == out and not set(kept[:ncache]) & out
+
+
 def test_version_and_status_strings(pkg):
     L = pkg.load_library()
     assert b"gfx950" in L.amt_version()

@@ -1,8 +1,8 @@
 // amt_api.hip -- core of the C-ABI of include/amt_advance_mu_t.h: errors, the bounds logic and
 // index normalisation (the job of advance_mu_t_no_async.cu:57-85 in the reference), the
 // device-resident entry points, the synthetic-input fill and the calibration copy.  The one-shot
-// host drop-in is amt_oneshot.hip, the resident handle amt_domain.hip, the RCCL slab stepper
-// amt_slab.hip.  There is deliberately no CPU compute path anywhere.
+// host drop-in is amt_oneshot.hip, the resident handle amt_domain.hip, the grid and slab steppers
+// amt_grid.hip.  There is deliberately no CPU compute path anywhere.
 #include "amt_internal.h"
 #include <atomic>
 
@@ -101,18 +101,14 @@ int amt_build_params(const AmtArgs<T> &a, AmtParams<T> &p, AmtWindow &w, bool *e
         return amt_fail(AMT_ERR_PRECONDITION,
                         "j window %d:%d plus halo not inside memory jms:jme=%d:%d",
                         w.j_start, w.j_end, a.jms, a.jme);
-    const void *ptrs[] = {a.ww, a.ww_1, a.u, a.u_1, a.v, a.v_1, a.mu, a.mut, a.muave, a.muts,
-                          a.muu, a.muv, a.mudf, a.t, a.t_1, a.t_ave, a.ft, a.mu_tend, a.dnw,
-                          a.fnm, a.fnp, a.rdnw, a.msfuy, a.msfvx_inv, a.msftx, a.msfty};
-    for (const void *q : ptrs)
+    const T *ptrs[AMT_F_COUNT];
+    amt_args_get_fields(a, ptrs);
+    for (const T *q : ptrs)
         if (!q) return amt_fail(AMT_ERR_INVALID_ARG, "null array pointer");
 
-    p.ww = a.ww; p.mu = a.mu; p.muave = a.muave; p.muts = a.muts; p.mudf = a.mudf;
-    p.t = a.t; p.t_ave = a.t_ave;
-    p.ww_1 = a.ww_1; p.u = a.u; p.u_1 = a.u_1; p.v = a.v; p.v_1 = a.v_1; p.mut = a.mut;
-    p.muu = a.muu; p.muv = a.muv; p.t_1 = a.t_1; p.ft = a.ft; p.mu_tend = a.mu_tend;
-    p.dnw = a.dnw; p.fnm = a.fnm; p.fnp = a.fnp; p.rdnw = a.rdnw; p.msfuy = a.msfuy;
-    p.msfvx_inv = a.msfvx_inv; p.msftx = a.msftx; p.msfty = a.msfty;
+#define AMT_FIELD_PARAM(ID, member, in, out) p.member = a.member;
+    AMT_FIELDS(AMT_FIELD_PARAM)
+#undef AMT_FIELD_PARAM
     p.rdx = a.rdx; p.rdy = a.rdy; p.dts = a.dts; p.epssm = a.epssm;
     p.idim = a.ime - a.ims + 1;
     p.kdim = a.kme - a.kms + 1;
@@ -165,7 +161,7 @@ static int amt_launch(hipStream_t stream, int variant, const AmtParams<T> &p)
     return AMT_OK;
 }
 
-// Only the first and the last row of the tile's window (amt_slab.hip: the two rows of a j-slab that
+// Only the first and the last row of the tile's window (amt_grid.hip: the two rows of a j-slab that
 // read a neighbour's halo), in one launch where the march kernel runs, in two otherwise.
 template <typename T>
 int amt_device_call_edges(void *hip_stream, int variant, const AmtArgs<T> &a)
@@ -216,7 +212,7 @@ int amt_device_call_ensemble(void *hip_stream, int variant, int members, const A
     return amt_launch<T>(static_cast<hipStream_t>(hip_stream), variant, p);
 }
 
-// The same launch when another stream's kernels are to run beside it (amt_slab.hip: the interior rows of a j-slab
+// The same launch when another stream's kernels are to run beside it (amt_grid.hip: the interior rows of a j-slab
 // while the halo exchange and the edge rows go through the communication stream).
 template <typename T>
 int amt_device_call_shared(void *hip_stream, int variant, const AmtArgs<T> &a)

@@ -1,4 +1,4 @@
-// amt_comm.h -- the halo-exchange engine the j-slab stepper (amt_slab.hip) and the i x j grid stepper (amt_grid.hip)
+// amt_comm.h -- the halo-exchange engine the j-slab stepper and the i x j grid stepper (both amt_grid.hip)
 // share (not installed).  An exchange is a fixed list of contiguous SEND segments (device pointer, bytes, destination
 // rank) and RECEIVE segments (device pointer, bytes, source rank) of one rank, set once at creation; between two ranks the
 // k-th segment one sends to the other is the k-th segment the other receives from it.  Two transports carry it:

@@ -388,7 +388,6 @@ static int amt_domain_tune(amt_domain *d, int tries, float *ms_per_try, bool pre
         explicit GuardPause(amt_domain *dom) : d(dom), every(dom->guard_every) { d->guard_every = 0; }
         ~GuardPause() { d->guard_every = every; }
     } pause(d);
-    static const int mutated[] = {AMT_F_WW, AMT_F_T, AMT_F_T_AVE, AMT_F_MU, AMT_F_MUAVE, AMT_F_MUTS, AMT_F_MUDF};
     auto bytes = [&](int f) { return d->count(f) * (size_t)d->dtype_bytes; };
     auto time_current = [&](float *ms) -> int {
         int rc = amt_domain_step(d, 1);
@@ -408,8 +407,8 @@ static int amt_domain_tune(amt_domain *d, int tries, float *ms_per_try, bool pre
     auto free_set = [](void **set) { for (int f = 0; f < AMT_F_COUNT; ++f) if (set[f]) { (void)hipFree(set[f]); set[f] = nullptr; } };
     hipError_t copy_err = hipSuccess;
     auto note = [&](hipError_t e) { if (e != hipSuccess && copy_err == hipSuccess) copy_err = e; };
-    for (int f : mutated) {
-        if (!preserve) break;
+    for (int f = 0; f < AMT_F_COUNT && preserve; ++f) {
+        if (!kAmtField[f].out) continue;                          // what the timed sweeps overwrite: the fields the routine assigns
         if (hipMalloc(&keep[f], bytes(f)) != hipSuccess) {
             (void)hipGetLastError();
             free_set(keep);
@@ -462,8 +461,8 @@ static int amt_domain_tune(amt_domain *d, int tries, float *ms_per_try, bool pre
             free_set(cand);
         }
     }
-    for (int f : mutated)                                         // contents as they were before the call
-        if (preserve) note(hipMemcpyAsync(d->field[f], keep[f], bytes(f), hipMemcpyDeviceToDevice, d->stream));
+    for (int f = 0; f < AMT_F_COUNT; ++f)                         // contents as they were before the call
+        if (keep[f]) note(hipMemcpyAsync(d->field[f], keep[f], bytes(f), hipMemcpyDeviceToDevice, d->stream));
     note(hipStreamSynchronize(d->stream));
     free_set(keep);
     if (copy_err != hipSuccess)

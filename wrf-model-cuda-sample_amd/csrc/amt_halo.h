@@ -1,7 +1,8 @@
 // amt_halo.h -- what crosses a patch edge, and the one kernel that moves it (not installed).  Everything that packs, unpacks,
 // refreshes or poisons halo cells -- the exchange segments and column buffers of amt_grid.hip, the host-owned messages
 // (DESIGN.md section 7.5), the cyclic refresh (amt_cyclic.hip, section 7.4), amt_domain_poison_halos -- reads THIS table and
-// launches amt_halo.hip's kernel (the poison: a fill of its own over the same cells).
+// launches amt_halo.hip's kernel (the poison: a fill of its own over the same cells).  The one-shot host call (amt_oneshot.hip)
+// reads the two row lists to know which arrays go up with a halo row.
 #pragma once
 #include "amt_internal.h"
 
@@ -25,6 +26,13 @@ constexpr AmtHaloFields kAmtHaloRecv[AMT_HALO_SIDES] = {
 };
 inline const AmtHaloFields &amt_halo_recv(int side) { return kAmtHaloRecv[side]; }
 inline const AmtHaloFields &amt_halo_sent(int side) { return kAmtHaloRecv[side ^ 1]; }
+
+inline bool amt_halo_receives(int side, int f)
+{
+    for (int q = 0; q < kAmtHaloRecv[side].n; ++q)
+        if (kAmtHaloRecv[side].field[q] == f) return true;
+    return false;
+}
 
 // memory levels of a field: kdim for a 3-D one, 1 for a 2-D one
 inline long amt_halo_levels(int f, long kdim) { return amt_field_rank(f) == 3 ? kdim : 1; }

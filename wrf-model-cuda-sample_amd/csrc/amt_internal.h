@@ -60,6 +60,52 @@ struct AmtArgs {
 };
 
 
+// ---------------------------------------------------------------------------
+// The field table: one row per AMT_F_* in the order of the enum (include/amt_synth.h) -- id, the AmtArgs member that carries
+// it (its name is the field's name), whether advance_mu_t reads it (`in`) and whether it assigns it (`out`).  t_ave
+// (module_small_step_em.f90:210) and muave, muts, mudf (:152-156) are assigned before any use; of ww only level 1 is read
+// (:161).  A field's rank is amt_field_rank(); the fields that need a halo row or column are the lists of amt_halo.h.
+// ---------------------------------------------------------------------------
+#define AMT_FIELDS(X)                                                                                              \
+    X(WW, ww, 1, 1) X(WW_1, ww_1, 1, 0) X(U, u, 1, 0) X(U_1, u_1, 1, 0) X(V, v, 1, 0) X(V_1, v_1, 1, 0)            \
+    X(MU, mu, 1, 1) X(MUT, mut, 1, 0) X(MUAVE, muave, 0, 1) X(MUTS, muts, 0, 1) X(MUU, muu, 1, 0) X(MUV, muv, 1, 0) \
+    X(MUDF, mudf, 0, 1) X(T, t, 1, 1) X(T_1, t_1, 1, 0) X(T_AVE, t_ave, 0, 1) X(FT, ft, 1, 0)                      \
+    X(MU_TEND, mu_tend, 1, 0) X(DNW, dnw, 1, 0) X(FNM, fnm, 1, 0) X(FNP, fnp, 1, 0) X(RDNW, rdnw, 1, 0)            \
+    X(MSFUY, msfuy, 1, 0) X(MSFVX_INV, msfvx_inv, 1, 0) X(MSFTX, msftx, 1, 0) X(MSFTY, msfty, 1, 0)
+
+struct AmtFieldRole {
+    int id;
+    const char *name;
+    bool in, out;
+};
+#define AMT_FIELD_ROW(ID, member, in, out) {AMT_F_##ID, #member, in != 0, out != 0},
+constexpr AmtFieldRole kAmtField[] = {AMT_FIELDS(AMT_FIELD_ROW)};
+#undef AMT_FIELD_ROW
+constexpr bool amt_field_table_in_order()
+{
+    int nwrong = 0;
+    for (int f = 0; f < AMT_F_COUNT; ++f) nwrong += kAmtField[f].id != f;
+    return nwrong == 0;
+}
+static_assert(sizeof kAmtField / sizeof *kAmtField == AMT_F_COUNT && amt_field_table_in_order(), "AMT_FIELDS must follow enum amt_field");
+inline const char *amt_field_name(int f) { return kAmtField[f].name; }
+
+// AmtArgs <-> an array of the AMT_F_COUNT array pointers, indexed by AMT_F_*
+template <typename T>
+inline void amt_args_get_fields(const AmtArgs<T> &a, const T *q[AMT_F_COUNT])
+{
+#define AMT_FIELD_GET(ID, member, in, out) q[AMT_F_##ID] = a.member;
+    AMT_FIELDS(AMT_FIELD_GET)
+#undef AMT_FIELD_GET
+}
+template <typename T>
+inline void amt_args_set_fields(AmtArgs<T> &a, T *const q[AMT_F_COUNT])
+{
+#define AMT_FIELD_SET(ID, member, in, out) a.member = q[AMT_F_##ID];
+    AMT_FIELDS(AMT_FIELD_SET)
+#undef AMT_FIELD_SET
+}
+
 // Checks the preconditions and rebases the Fortran bounds to memory-relative zero-based ones;
 // *empty is set when the compute window holds no column (amt_api.hip).
 template <typename T> int amt_build_params(const AmtArgs<T> &a, AmtParams<T> &p, AmtWindow &w, bool *empty);
@@ -109,7 +155,7 @@ extern template int amt_device_call_edges<double>(void *, int, const AmtArgs<dou
 
 
 // ---------------------------------------------------------------------------
-// resident domain handle (amt_domain.hip), also stepped by the slab stepper (amt_slab.hip)
+// resident domain handle (amt_domain.hip), also stepped by the grid and slab steppers (amt_grid.hip)
 // ---------------------------------------------------------------------------
 namespace {
 // makes the domain's device current for the duration of a call and restores the caller's
@@ -162,16 +208,8 @@ struct amt_ensemble {
 template <typename T>
 inline void amt_domain_args(amt_domain *d, AmtArgs<T> &a)
 {
-    T **f = reinterpret_cast<T **>(d->field);
-    a.ww = f[AMT_F_WW]; a.ww_1 = f[AMT_F_WW_1]; a.u = f[AMT_F_U]; a.u_1 = f[AMT_F_U_1];
-    a.v = f[AMT_F_V]; a.v_1 = f[AMT_F_V_1]; a.mu = f[AMT_F_MU]; a.mut = f[AMT_F_MUT];
-    a.muave = f[AMT_F_MUAVE]; a.muts = f[AMT_F_MUTS]; a.muu = f[AMT_F_MUU]; a.muv = f[AMT_F_MUV];
-    a.mudf = f[AMT_F_MUDF]; a.t = f[AMT_F_T]; a.t_1 = f[AMT_F_T_1]; a.t_ave = f[AMT_F_T_AVE];
-    a.ft = f[AMT_F_FT]; a.mu_tend = f[AMT_F_MU_TEND];
+    amt_args_set_fields(a, reinterpret_cast<T *const *>(d->field));
     a.rdx = (T)d->rdx; a.rdy = (T)d->rdy; a.dts = (T)d->dts; a.epssm = (T)d->epssm;
-    a.dnw = f[AMT_F_DNW]; a.fnm = f[AMT_F_FNM]; a.fnp = f[AMT_F_FNP]; a.rdnw = f[AMT_F_RDNW];
-    a.msfuy = f[AMT_F_MSFUY]; a.msfvx_inv = f[AMT_F_MSFVX_INV]; a.msftx = f[AMT_F_MSFTX];
-    a.msfty = f[AMT_F_MSFTY];
     a.periodic_x = d->periodic_x; a.specified = d->specified; a.nested = d->nested;
     a.ids = d->ids; a.ide = d->ide; a.jds = d->jds; a.jde = d->jde; a.kde = d->kde;
     a.ims = d->ims; a.ime = d->ime; a.jms = d->jms; a.jme = d->jme; a.kms = d->kms; a.kme = d->kme;

@@ -1,7 +1,8 @@
 // amt_oneshot.hip -- the one-shot host drop-in amt_advance_mu_t_f32/_f64: host arrays in, host
 // arrays out (the job of the reference's CUDA wrapper, advance_mu_t_no_async.cu:178-423: alloc,
 // H2D, launch, D2H, free), streamed.
-#include "amt_internal.h"
+#include "amt_halo.h"
+#include "amt_oneshot_plan.h"
 #include <chrono>
 #include <condition_variable>
 #include <functional>
@@ -13,11 +14,48 @@
 #include <unistd.h>
 
 namespace {
-int amt_env_flag(const char *name, int dflt)
+// The arrays a thread may keep on the device between calls (HostWorkspace::Kept): first the cached inputs, then the
+// deferrable outputs -- exactly the fields the routine assigns (amt_internal.h's table).  Rank and name of an entry are its field's.
+constexpr int kKeepField[] = {AMT_F_WW_1, AMT_F_U_1, AMT_F_V_1, AMT_F_T_1, AMT_F_FT, AMT_F_MUT, AMT_F_MUU, AMT_F_MUV, AMT_F_MU_TEND,
+                              AMT_F_MSFUY, AMT_F_MSFVX_INV, AMT_F_MSFTX, AMT_F_MSFTY, AMT_F_DNW, AMT_F_FNM, AMT_F_FNP, AMT_F_RDNW,
+                              /* deferred: */ AMT_F_WW, AMT_F_T, AMT_F_T_AVE, AMT_F_MU, AMT_F_MUAVE, AMT_F_MUTS, AMT_F_MUDF};
+constexpr int NKEEP = sizeof kKeepField / sizeof *kKeepField;
+constexpr int NCACHE = 17;                                    // the first NCACHE entries are the cached inputs
+constexpr bool amt_keep_table_ok()
 {
-    const char *v = getenv(name);
-    return (v && *v) ? atoi(v) : dflt;
+    int nout = 0, nwrong = 0;
+    for (int f = 0; f < AMT_F_COUNT; ++f) nout += kAmtField[f].out;
+    for (int r = 0; r < NKEEP; ++r) nwrong += kAmtField[kKeepField[r]].out != (r >= NCACHE);
+    return nwrong == 0 && NKEEP - NCACHE == nout;
 }
+static_assert(amt_keep_table_ok(), "kKeepField: NCACHE read-only inputs, then every field the routine assigns");
+inline int amt_keep_rank(int r) { return amt_field_rank(kKeepField[r]); }
+inline const char *amt_keep_name(int r) { return amt_field_name(kKeepField[r]); }
+
+// The window's cells of an array with memory rows of idim elements (and kdim levels): columns i0 .. i0+ni-1, levels k1 .. k1+nk-1.
+struct WindowCells {
+    size_t es = 0;                                            // element size
+    long idim = 0, kdim = 0, i0 = 0, ni = 0, k1 = 0, nk = 0;
+};
+// nj rows of those cells of a rank-3 or rank-2 array, device to host: row `drow` of the device array lands in row `hrow` of the host array
+hipError_t amt_window_down(const WindowCells &g, int rank, void *host, size_t hrow, const void *dev, size_t drow, size_t nj, hipStream_t st)
+{
+    const size_t pitch = (size_t)g.idim * g.es;
+    if (rank == 2)
+        return hipMemcpy2DAsync(static_cast<char *>(host) + hrow * pitch + (size_t)g.i0 * g.es, pitch,
+                                static_cast<const char *>(dev) + drow * pitch + (size_t)g.i0 * g.es, pitch, (size_t)g.ni * g.es, nj,
+                                hipMemcpyDeviceToHost, st);
+    hipMemcpy3DParms cp;
+    memset(&cp, 0, sizeof cp);
+    cp.srcPtr = make_hipPitchedPtr(const_cast<void *>(dev), pitch, (size_t)g.idim, (size_t)g.kdim);
+    cp.dstPtr = make_hipPitchedPtr(host, pitch, (size_t)g.idim, (size_t)g.kdim);
+    cp.srcPos = make_hipPos((size_t)g.i0 * g.es, (size_t)g.k1, drow);
+    cp.dstPos = make_hipPos((size_t)g.i0 * g.es, (size_t)g.k1, hrow);
+    cp.extent = make_hipExtent((size_t)g.ni * g.es, (size_t)g.nk, nj);
+    cp.kind = hipMemcpyDeviceToHost;
+    return hipMemcpy3DAsync(&cp, st);
+}
+
 // What a one-shot call needs on the device besides the data: three streams, six events and a
 // buffer arena.  Creating and destroying them costs ~10 ms per call -- more than the whole call
 // at WRF patch sizes -- so each host thread keeps its own set between calls (per thread: WRF
@@ -27,7 +65,7 @@ struct HostWorkspace {
     hipStream_t up = nullptr, comp = nullptr, down = nullptr;
     hipEvent_t uploaded[2] = {}, computed[2] = {}, drained[2] = {};
     char *arena = nullptr;
-    size_t arena_size = 0, used = 0;
+    size_t arena_size = 0;
     char *stage = nullptr;                                   // page-locked host staging (packed calls)
     size_t stage_size = 0;
     static constexpr size_t keep_limit = (size_t)1 << 30;   // larger arenas are not kept between calls
@@ -42,8 +80,6 @@ struct HostWorkspace {
     //    the device copy is the truth until amt_host_fetch brings the window's cells down (or amt_host_invalidate
     //    says the host array was rewritten and is the truth again); the in/out ones (level 1 of ww, t, mu) go up
     //    only while the device copy is not valid.
-    static constexpr int NKEEP = 24;
-    static constexpr int NCACHE = 17;                         // the first NCACHE entries are the cached inputs
     struct Kept {
         bool enabled = false, check = false;                  // cache on; checksum / canary debug mode
         bool defer_all = false;
@@ -59,8 +95,8 @@ struct HostWorkspace {
         const void *host[NKEEP] = {};
         int key[16] = {};                                     // element size, extents, window, device
         // geometry of the window the copies cover (amt_host_fetch works from it)
-        size_t esize = 0;
-        long idim = 0, kdim = 0, i0 = 0, ni = 0, k1 = 0, nk = 0, j_start = 0, j_end = 0, jms = 0;
+        WindowCells cells;
+        long j_start = 0, j_end = 0, jms = 0;
         bool deferred(const void *ptr) const
         {
             if (defer_all) return true;
@@ -131,14 +167,7 @@ struct HostWorkspace {
             if (e != hipSuccess) { (void)hipGetLastError(); arena = nullptr; return e; }
             arena_size = bytes;
         }
-        used = 0;
         return hipSuccess;
-    }
-    void *take(size_t bytes)
-    {
-        const size_t off = (used + 255) & ~(size_t)255;
-        used = off + bytes;
-        return arena + off;
     }
     hipError_t stage_reserve(size_t bytes)
     {
@@ -171,16 +200,6 @@ struct WorkspaceScope {
 };
 }  // namespace
 
-
-// item index (argument position among the 26 arrays) and rank of every kept field: first the cached inputs, then the
-// deferrable outputs
-static const int kKeepField[HostWorkspace::NKEEP] = {1, 3, 5, 14, 16, 7, 10, 11, 17, 22, 23, 24, 25, 18, 19, 20, 21,
-                                                     /* deferred: */ 0, 13, 15, 6, 8, 9, 12};
-static const int kKeepRank[HostWorkspace::NKEEP] = {3, 3, 3, 3, 3, 2, 2, 2, 2, 2, 2, 2, 2, 1, 1, 1, 1, 3, 3, 3, 2, 2, 2, 2};
-static const char *const kKeepName[HostWorkspace::NKEEP] = {"ww_1", "u_1", "v_1", "t_1", "ft", "mut", "muu", "muv", "mu_tend", "msfuy",
-                                                            "msfvx_inv", "msftx", "msfty", "dnw", "fnm", "fnp", "rdnw",
-                                                            "ww", "t", "t_ave", "mu", "muave", "muts", "mudf"};
-
 // 64-bit checksum of a byte range (check mode only: it reads the whole range; byte-wise loads of the head and tail,
 // memcpy-based word loads in between: the range need not be 8-byte aligned)
 static uint64_t amt_host_sum(const void *p, size_t bytes)
@@ -209,25 +228,10 @@ hipError_t amt_keep_fetch(HostWorkspace &ws, int r)
 {
     HostWorkspace::Kept &k = ws.res;
     if (!k.buf[r] || !k.stale[r]) return hipSuccess;
-    char *host = static_cast<char *>(const_cast<void *>(k.host[r]));
-    const size_t es = k.esize, idim = (size_t)k.idim, kdim = (size_t)k.kdim;
-    const size_t nj = (size_t)(k.j_end - k.j_start + 1);
-    hipError_t e;
-    if (kKeepRank[r] == 3) {
-        if (k.nk <= 0) { k.stale[r] = false; return hipSuccess; }
-        hipMemcpy3DParms cp;
-        memset(&cp, 0, sizeof cp);
-        cp.srcPtr = make_hipPitchedPtr(k.buf[r], idim * es, idim, kdim);
-        cp.dstPtr = make_hipPitchedPtr(host, idim * es, idim, kdim);
-        cp.srcPos = make_hipPos((size_t)k.i0 * es, (size_t)k.k1, 1);
-        cp.dstPos = make_hipPos((size_t)k.i0 * es, (size_t)k.k1, (size_t)(k.j_start - k.jms));
-        cp.extent = make_hipExtent((size_t)k.ni * es, (size_t)k.nk, nj);
-        cp.kind = hipMemcpyDeviceToHost;
-        e = hipMemcpy3DAsync(&cp, ws.down);
-    } else {
-        e = hipMemcpy2DAsync(host + ((size_t)(k.j_start - k.jms) * idim + (size_t)k.i0) * es, idim * es,
-                             k.buf[r] + (idim + (size_t)k.i0) * es, idim * es, (size_t)k.ni * es, nj, hipMemcpyDeviceToHost, ws.down);
-    }
+    void *host = const_cast<void *>(k.host[r]);
+    const size_t nj = (size_t)(k.j_end - k.j_start + 1), hrow = (size_t)(k.j_start - k.jms);
+    if (amt_keep_rank(r) == 3 && k.cells.nk <= 0) { k.stale[r] = false; return hipSuccess; }
+    hipError_t e = amt_window_down(k.cells, amt_keep_rank(r), host, hrow, k.buf[r], 1, nj, ws.down);
     if (e == hipSuccess) e = hipStreamSynchronize(ws.down);
     if (e == hipSuccess) k.stale[r] = false;
     return e;
@@ -239,12 +243,13 @@ hipError_t amt_keep_fetch(HostWorkspace &ws, int r)
 bool amt_keep_canary(HostWorkspace::Kept &k, int r, bool fill)
 {
     char *host = static_cast<char *>(const_cast<void *>(k.host[r]));
-    const size_t es = k.esize, idim = (size_t)k.idim, kdim = (size_t)k.kdim;
-    const size_t levels = kKeepRank[r] == 3 ? (size_t)k.nk : 1, kd = kKeepRank[r] == 3 ? kdim : 1, k1 = kKeepRank[r] == 3 ? (size_t)k.k1 : 0;
+    const WindowCells &g = k.cells;
+    const bool r3 = amt_keep_rank(r) == 3;
+    const size_t es = g.es, idim = (size_t)g.idim, levels = r3 ? (size_t)g.nk : 1, kd = r3 ? (size_t)g.kdim : 1, k1 = r3 ? (size_t)g.k1 : 0;
     for (long j = k.j_start; j <= k.j_end; ++j)
         for (size_t l = 0; l < levels; ++l) {
-            char *row = host + ((((size_t)(j - k.jms)) * kd + k1 + l) * idim + (size_t)k.i0) * es;
-            for (long i = 0; i < k.ni; ++i) {
+            char *row = host + ((((size_t)(j - k.jms)) * kd + k1 + l) * idim + (size_t)g.i0) * es;
+            for (long i = 0; i < g.ni; ++i) {
                 if (fill) {
                     if (es == 8) memcpy(row + (size_t)i * 8, &kCanary64, 8);
                     else memcpy(row + (size_t)i * 4, &kCanary32, 4);
@@ -261,7 +266,7 @@ int amt_keep_flush(HostWorkspace &ws)
 {
     if (ws.device < 0 || !ws.res.any_stale()) return AMT_OK;
     DeviceScope dev(ws.device);
-    for (int r = 0; r < HostWorkspace::NKEEP; ++r) AMT_HIP(amt_keep_fetch(ws, r));
+    for (int r = 0; r < NKEEP; ++r) AMT_HIP(amt_keep_fetch(ws, r));
     return AMT_OK;
 }
 }  // namespace
@@ -280,7 +285,7 @@ static int host_cache_enable_local(int on)
         DeviceScope dev(ws.device);
         for (hipStream_t st : {ws.up, ws.comp, ws.down})
             if (st) (void)hipStreamSynchronize(st);
-        for (int r = 0; r < HostWorkspace::NCACHE; ++r) {        // the cached inputs go; deferred outputs are another setting
+        for (int r = 0; r < NCACHE; ++r) {        // the cached inputs go; deferred outputs are another setting
             if (ws.res.buf[r]) (void)hipFree(ws.res.buf[r]);
             ws.res.buf[r] = nullptr; ws.res.bytes[r] = 0; ws.res.active[r] = ws.res.valid[r] = false; ws.res.host[r] = nullptr;
         }
@@ -300,7 +305,7 @@ static int host_invalidate_local(const void *host_ptr)
     // "the host array was rewritten": a cached input goes up again with the next call; for a deferred output the HOST
     // is the truth again (whatever the device still held for it is given up)
     HostWorkspace::Kept &r = tl_workspace.res;
-    for (int q = 0; q < HostWorkspace::NKEEP; ++q)
+    for (int q = 0; q < NKEEP; ++q)
         if (!host_ptr || r.host[q] == host_ptr) { r.valid[q] = false; r.stale[q] = false; r.poisoned[q] = false; }
     return AMT_OK;                                            // an array that is not kept is uploaded anyway
 }
@@ -317,7 +322,7 @@ static int host_defer_local(const void *host_ptr, int on)
         return AMT_OK;
     }
     // off: what the device holds for it comes down first, then the array is an ordinary output again
-    for (int r = HostWorkspace::NCACHE; r < HostWorkspace::NKEEP; ++r)
+    for (int r = NCACHE; r < NKEEP; ++r)
         if (k.buf[r] && (!host_ptr || k.host[r] == host_ptr)) {
             if (k.stale[r] && ws.device >= 0) {
                 DeviceScope dev(ws.device);
@@ -337,11 +342,11 @@ static int host_fetch_local(const void *host_ptr)
     HostWorkspace &ws = tl_workspace;
     if (ws.device < 0) return AMT_OK;
     DeviceScope dev(ws.device);
-    for (int r = HostWorkspace::NCACHE; r < HostWorkspace::NKEEP; ++r)
+    for (int r = NCACHE; r < NKEEP; ++r)
         if ((!host_ptr || ws.res.host[r] == host_ptr) && ws.res.poisoned[r])
             return amt_fail(AMT_ERR_PRECONDITION, "deferred output %s: its device copy is undefined since a call failed part-way (some rows may be "
-                            "a sub-step ahead); nothing is brought down -- amt_host_invalidate(ptr) makes the host array the truth again", kKeepName[r]);
-    for (int r = HostWorkspace::NCACHE; r < HostWorkspace::NKEEP; ++r)
+                            "a sub-step ahead); nothing is brought down -- amt_host_invalidate(ptr) makes the host array the truth again", amt_keep_name(r));
+    for (int r = NCACHE; r < NKEEP; ++r)
         if (!host_ptr || ws.res.host[r] == host_ptr) AMT_HIP(amt_keep_fetch(ws, r));
     return AMT_OK;
 }
@@ -349,9 +354,9 @@ static int host_fetch_local(const void *host_ptr)
 static int host_stale_local(const void *host_ptr)
 {
     const HostWorkspace::Kept &k = tl_workspace.res;
-    for (int r = HostWorkspace::NCACHE; r < HostWorkspace::NKEEP; ++r)
+    for (int r = NCACHE; r < NKEEP; ++r)
         if (k.poisoned[r] && (!host_ptr || k.host[r] == host_ptr)) return -1;      // undefined after a failed call
-    for (int r = HostWorkspace::NCACHE; r < HostWorkspace::NKEEP; ++r)
+    for (int r = NCACHE; r < NKEEP; ++r)
         if (k.stale[r] && (!host_ptr || k.host[r] == host_ptr)) return 1;
     return 0;
 }
@@ -399,343 +404,328 @@ extern "C" int amt_host_unpin(void *ptr)
     return AMT_OK;
 }
 
+namespace {
+double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// A call that fails after its first kernel went out leaves the deferred in/out copies (level 1 of ww, t, mu: advanced in place,
+// chunk by chunk) partly a sub-step ahead: a retry would apply the sub-step twice to those rows and a fetch would bring a
+// half-advanced state down.  They are marked undefined.
+struct FailGuard {
+    HostWorkspace::Kept &k;
+    bool launched = false, ok = false;
+    ~FailGuard()
+    {
+        if (!launched || ok) return;
+        for (int r = NCACHE; r < NKEEP; ++r)
+            if (k.active[r] && (k.stale[r] || k.valid[r])) { k.valid[r] = k.stale[r] = false; k.poisoned[r] = true; }
+    }
+};
+
+// download thread: takes chunks in order as the main thread reports them launched, reports them drained so that their buffer
+// set can be reused
+struct Downloader {
+    std::thread th;
+    std::mutex m;
+    std::condition_variable cv;
+    int n_launched = 0, n_drained = 0;
+    bool stop = false;
+    hipError_t err = hipSuccess;
+    // false: no thread to be had
+    bool start(int device, int nchunk, std::function<hipError_t(int)> download_and_wait)
+    {
+        try {
+            th = std::thread([this, device, nchunk, download_and_wait] {
+                hipError_t e = hipSetDevice(device);
+                for (int c = 0; c < nchunk; ++c) {
+                    {
+                        std::unique_lock<std::mutex> lk(m);
+                        cv.wait(lk, [&] { return stop || n_launched > c; });
+                        if (n_launched <= c) return;
+                    }
+                    if (e == hipSuccess) e = download_and_wait(c);
+                    {
+                        std::lock_guard<std::mutex> lk(m);
+                        if (e != hipSuccess) err = e;
+                        n_drained = c + 1;
+                    }
+                    cv.notify_all();
+                }
+            });
+        } catch (const std::exception &) {
+            return false;
+        }
+        return true;
+    }
+    void launched(int c)
+    {
+        { std::lock_guard<std::mutex> lk(m); n_launched = c + 1; }
+        cv.notify_all();
+    }
+    bool wait_drained(int c)                                  // false: a download failed
+    {
+        std::unique_lock<std::mutex> lk(m);
+        cv.wait(lk, [&] { return n_drained > c; });
+        return err == hipSuccess;
+    }
+    hipError_t finish()                                       // all launched chunks drain, then the thread ends
+    {
+        { std::lock_guard<std::mutex> lk(m); stop = true; }
+        cv.notify_all();
+        if (th.joinable()) th.join();
+        return err;
+    }
+    ~Downloader() { (void)finish(); }
+};
+
+// ---- the per-call context: what the stages below share
 template <typename T>
-static int amt_host_call(const AmtArgs<T> &h)
-{
+struct Oneshot {
+    const AmtArgs<T> &h;
     AmtParams<T> p;
     AmtWindow w;
-    bool empty = false;
-    int rc = amt_build_params(h, p, w, &empty);
-    if (rc != AMT_OK || empty) return rc;
-    int ndev = 0;
-    AMT_HIP(hipGetDeviceCount(&ndev));
-    if (ndev < 1) return amt_fail(AMT_ERR_NO_DEVICE, "no HIP device visible");
     int device = 0;
-    AMT_HIP(hipGetDevice(&device));
-
-    const long idim = p.idim, kdim = p.kdim;
-    const size_t r3 = (size_t)idim * kdim, r2 = (size_t)idim, n1 = (size_t)kdim;   // elements per j row
-    const int nj = w.j_end - w.j_start + 1;
-    const size_t ni = (size_t)(p.i1 - p.i0 + 1);
-
-    // `out`: assigned by the routine; `in`: read by it (t_ave :210 and muave, muts, mudf :152-156
-    // are assigned before any use; of ww only level 1 is read, :161)
-    struct Item { const T *host; int rank; bool halo; bool out; bool in; };
-    enum { F_WW = 0 };
-    const Item items[26] = {
-        {h.ww, 3, false, true, true}, {h.ww_1, 3, false, false, true}, {h.u, 3, false, false, true},
-        {h.u_1, 3, false, false, true}, {h.v, 3, true, false, true}, {h.v_1, 3, true, false, true},
-        {h.mu, 2, false, true, true}, {h.mut, 2, false, false, true}, {h.muave, 2, false, true, false},
-        {h.muts, 2, false, true, false}, {h.muu, 2, false, false, true}, {h.muv, 2, true, false, true},
-        {h.mudf, 2, false, true, false}, {h.t, 3, false, true, true}, {h.t_1, 3, true, false, true},
-        {h.t_ave, 3, false, true, false}, {h.ft, 3, false, false, true}, {h.mu_tend, 2, false, false, true},
-        {h.dnw, 1, false, false, true}, {h.fnm, 1, false, false, true}, {h.fnp, 1, false, false, true},
-        {h.rdnw, 1, false, false, true}, {h.msfuy, 2, false, false, true}, {h.msfvx_inv, 2, true, false, true},
-        {h.msftx, 2, false, false, true}, {h.msfty, 2, false, false, true},
-    };
-    bool pinned = true, pinned_small = true;                  // the 3-D arrays / the 2-D and 1-D ones
-    for (const Item &it : items) (it.rank == 3 ? pinned : pinned_small) &= amt_is_pinned(it.host);
-
-    // 3-D arrays that are kept on the device between calls (cached inputs, deferred outputs: below) need no chunk buffers
-    bool keep_want[26] = {};
-    int nbig = 10;
-    for (int r = 0; r < HostWorkspace::NKEEP; ++r) {
-        const int f = kKeepField[r];
-        keep_want[f] = r < HostWorkspace::NCACHE ? tl_workspace.res.enabled : tl_workspace.res.deferred(items[f].host);
-        if (keep_want[f] && items[f].rank == 3) --nbig;
-    }
-    // chunking: ~320 MB of 3-D arrays per chunk (measured best at 1024x60x1024 fp64), counting the arrays that stream
-    const char *env_rows = getenv("AMT_STREAM_ROWS");         // test/tuning knob: rows per chunk
-    const bool may_thread = !pinned && amt_env_flag("AMT_STREAM_THREAD", 1);
-    long rows = env_rows ? atol(env_rows) : (pinned || may_thread) ? (long)((320u << 20) / (r3 * sizeof(T) * (size_t)(nbig > 0 ? nbig : 1)) + 1) : (long)nj;
-    if (rows < 1) rows = 1;
-    if (rows > nj) rows = nj;
-    const int nchunk = (int)((nj + rows - 1) / rows);
-    const int nset = nchunk > 1 ? 2 : 1;
-    const size_t crow = (size_t)rows + 2;                     // device rows per 3-D buffer set
-    const size_t wrow = (size_t)nj + 2;                       // device rows of a 2-D array: the window's +-1
-    bool threaded = may_thread && nchunk > 1;
-
-    // packing (see above): the small arrays when they are pageable, the 3-D ones too when they
-    // are pageable, one chunk and small
-    const size_t small_bytes = 12 * (r2 * wrow * sizeof(T) + 256) + 4 * (n1 * sizeof(T) + 256);
-    const size_t big_bytes = (size_t)nset * nbig * (r3 * crow * sizeof(T) + 256);
-    const bool allow_pack = amt_env_flag("AMT_STREAM_PACK", 1) != 0;
-    const bool pack_small = allow_pack && !pinned_small && small_bytes <= ((size_t)32 << 20);
-    const bool pack_big = pack_small && !pinned && nchunk == 1 && big_bytes <= ((size_t)64 << 20);
-
-    const bool trace = getenv("AMT_STREAM_TRACE") != nullptr;
-    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_begin = now();
-
-    // arena layout: [3-D inputs][3-D outputs][small outputs][small inputs] -- what comes down is
-    // one contiguous range, and so is everything a packed call sends up
     HostWorkspace &ws = tl_workspace;
-    // Test hook (tests/test_gpu_20_host_cache.py, the one-GPU twin of the two-device test): AMT_TEST_PRETEND_DEVICE_CHANGE=n makes
-    // the n-th one-shot call of a thread behave as if the thread had moved to another device since its last call -- the workspace
-    // of the "old" device is given up exactly as prepare() gives it up, only the device number stays the same.
-    const long calls_of_this_thread = ++tl_oneshot_calls;
-    const char *pretend_env = getenv("AMT_TEST_PRETEND_DEVICE_CHANGE");
-    const bool pretend_move = pretend_env && *pretend_env && atol(pretend_env) == calls_of_this_thread && ws.device >= 0;
-    if (ws.device >= 0 && (ws.device != device || pretend_move) && ws.res.any_stale()) {
-        // the thread moved to another device: prepare() gives the old device's workspace up, and deferred outputs whose only
-        // current copy lives there must come down to their host arrays first (nothing the device alone holds is ever dropped,
-        // ADVICE r04) -- on the OLD device, whose streams still exist
-        rc = amt_keep_flush(ws);
-        if (rc != AMT_OK) return rc;
-    }
-    if (pretend_move) ws.release();                           // what prepare() does when device != ws.device
-    {
-        const hipError_t e = ws.prepare(device, big_bytes + small_bytes);
-        if (e == hipErrorOutOfMemory) return amt_fail(AMT_ERR_ALLOC, "hipMalloc of %zu bytes failed", big_bytes + small_bytes);
-        AMT_HIP(e);
-    }
-    WorkspaceScope scope{ws};                                 // drains the three streams on every way out
-    T *dev[2][26];
-    size_t out3_begin = 0, small_begin = 0, small_out_end = 0;
-    for (int pass = 0; pass < 4; ++pass) {
-        if (pass == 1) out3_begin = (ws.used + 255) & ~(size_t)255;
-        if (pass == 2) small_begin = (ws.used + 255) & ~(size_t)255;
-        if (pass == 3) small_out_end = (ws.used + 255) & ~(size_t)255;
-        for (int f = 0; f < 26; ++f) {
-            const Item &it = items[f];
-            const bool big = it.rank == 3;
-            if (big != (pass < 2) || it.out != (pass == 1 || pass == 2)) continue;
-            if (big && keep_want[f]) {
-                dev[0][f] = dev[1][f] = nullptr;              // lives in its kept whole-window copy
-            } else if (big) {
-                for (int s = 0; s < nset; ++s) dev[s][f] = static_cast<T *>(ws.take(r3 * crow * sizeof(T)));
-                if (nset == 1) dev[1][f] = dev[0][f];
-            } else {
-                dev[0][f] = dev[1][f] = static_cast<T *>(ws.take((it.rank == 2 ? r2 * wrow : n1) * sizeof(T)));
-            }
-        }
-    }
-    const size_t arena_end = ws.used;
-
-    // ---- arrays kept on the device between calls: cached inputs and deferred outputs (whole-window copies) -----
-    int res_of[26];
-    for (int f = 0; f < 26; ++f) res_of[f] = -1;
     HostWorkspace::Kept &res = ws.res;
-    bool res_upload[HostWorkspace::NKEEP] = {};
-    long res_hi[HostWorkspace::NKEEP];                         // highest row uploaded so far in this call
-    for (int r = 0; r < HostWorkspace::NKEEP; ++r) res_hi[r] = (long)w.j_start - 2;
+    const T *host[AMT_F_COUNT];
+    bool halo[AMT_F_COUNT];                                   // goes up with the rows below and above its chunk (amt_halo.h)
+    bool keep_want[AMT_F_COUNT] = {};                         // stays on the device between calls under the current settings
+    bool pinned = true, pinned_small = true;                  // the 3-D arrays / the 2-D and 1-D ones
+    size_t r3, r2, n1, ni;                                    // elements per j row of a 3-D / 2-D array, of a 1-D array; window columns
+    int nj;
+    WindowCells cells;
+    Plan pl;
+    Arena ar;
+    T *dev[2][AMT_F_COUNT];
+    int res_of[AMT_F_COUNT];                                  // kept entry of a field, -1: not kept
+    bool res_upload[NKEEP] = {};
+    long res_hi[NKEEP];                                       // highest row uploaded so far in this call
+    char *stage = nullptr;                                    // staging buffer: mirrors the arena from stage_base on
+    size_t stage_base = 0;
+    FailGuard fail_guard{res};
+
+    explicit Oneshot(const AmtArgs<T> &args) : h(args) {}
+    T *kept(int f) const { return reinterpret_cast<T *>(res.buf[res_of[f]]); }
+    T *staged(const T *devptr) const                          // the staging twin of a device address
     {
-        bool want[HostWorkspace::NKEEP];
+        return reinterpret_cast<T *>(stage + ((reinterpret_cast<const char *>(devptr) - ws.arena) - stage_base));
+    }
+    struct Chunk { int s, c0, c1; };                          // chunk c: buffer set s, rows c0..c1 of the window
+    Chunk chunk(int c) const
+    {
+        const int c0 = w.j_start + (int)(c * pl.rows);
+        return {c % pl.nset, c0, (c0 + pl.rows - 1 < w.j_end) ? (int)(c0 + pl.rows - 1) : w.j_end};
+    }
+
+    // ---- stage: the arrays, the plan and the layout of this call (pointer queries and host arithmetic)
+    void describe()
+    {
+        amt_args_get_fields(h, host);
+        r3 = (size_t)p.idim * p.kdim; r2 = (size_t)p.idim; n1 = (size_t)p.kdim;
+        nj = w.j_end - w.j_start + 1;
+        ni = (size_t)(p.i1 - p.i0 + 1);
+        cells.es = sizeof(T); cells.idim = p.idim; cells.kdim = p.kdim; cells.i0 = p.i0; cells.ni = (long)ni; cells.k1 = p.k1; cells.nk = p.nk;
+        int nbig = 0;                                         // 3-D arrays that need chunk buffers: all but the kept ones
+        for (int f = 0; f < AMT_F_COUNT; ++f) {
+            halo[f] = amt_halo_receives(AMT_HALO_BELOW, f) || amt_halo_receives(AMT_HALO_ABOVE, f);
+            (amt_field_rank(f) == 3 ? pinned : pinned_small) &= amt_is_pinned(host[f]);
+            nbig += amt_field_rank(f) == 3;
+        }
+        for (int r = 0; r < NKEEP; ++r) {
+            const int f = kKeepField[r];
+            keep_want[f] = r < NCACHE ? res.enabled : res.deferred(host[f]);
+            if (keep_want[f] && amt_field_rank(f) == 3) --nbig;
+        }
+        pl = oneshot_plan(r3, r2, n1, nj, sizeof(T), pinned, pinned_small, nbig);
+        ar = oneshot_layout(pl, r3, r2, n1, sizeof(T), keep_want);
+    }
+
+    // ---- stage: the thread's workspace on this device, with an arena of the planned size
+    int acquire()
+    {
+        // Test hook (tests/test_gpu_20_host_cache.py, the one-GPU twin of the two-device test): AMT_TEST_PRETEND_DEVICE_CHANGE=n makes
+        // the n-th one-shot call of a thread behave as if the thread had moved to another device since its last call -- the workspace
+        // of the "old" device is given up exactly as prepare() gives it up, only the device number stays the same.
+        const long calls_of_this_thread = ++tl_oneshot_calls;
+        const char *pretend_env = getenv("AMT_TEST_PRETEND_DEVICE_CHANGE");
+        const bool pretend_move = pretend_env && *pretend_env && atol(pretend_env) == calls_of_this_thread && ws.device >= 0;
+        if (ws.device >= 0 && (ws.device != device || pretend_move) && ws.res.any_stale()) {
+            // the thread moved to another device: prepare() gives the old device's workspace up, and deferred outputs whose only
+            // current copy lives there must come down to their host arrays first (nothing the device alone holds is ever dropped,
+            // ADVICE r04) -- on the OLD device, whose streams still exist
+            const int rc = amt_keep_flush(ws);
+            if (rc != AMT_OK) return rc;
+        }
+        if (pretend_move) ws.release();                       // what prepare() does when device != ws.device
+        const hipError_t e = ws.prepare(device, pl.big_bytes + pl.small_bytes);
+        if (e == hipErrorOutOfMemory) return amt_fail(AMT_ERR_ALLOC, "hipMalloc of %zu bytes failed", pl.big_bytes + pl.small_bytes);
+        AMT_HIP(e);
+        for (int s = 0; s < 2; ++s)
+            for (int f = 0; f < AMT_F_COUNT; ++f)
+                dev[s][f] = ar.off[s][f] == kNoSlot ? nullptr : reinterpret_cast<T *>(ws.arena + ar.off[s][f]);
+        return AMT_OK;
+    }
+
+    // checksum of exactly the rows a call uploads of cached field f (rows j_start-1 / j_end+1 of a 3-D one only for the halo arrays)
+    uint64_t uploaded_sum(int f) const
+    {
+        const int lo = halo[f] ? w.j_start - 1 : w.j_start, hi = halo[f] ? w.j_end + 1 : w.j_end;
+        const int rank = amt_field_rank(f);
+        return rank == 3 ? amt_host_sum(host[f] + (size_t)(lo - h.jms) * r3, (size_t)(hi - lo + 1) * r3 * sizeof(T))
+             : rank == 2 ? amt_host_sum(host[f] + (size_t)(w.j_start - 1 - h.jms) * r2, r2 * pl.wrow * sizeof(T))
+                         : amt_host_sum(host[f], n1 * sizeof(T));
+    }
+
+    // ---- stage: kept arrays, open.  Cached inputs and deferred outputs (whole-window copies): re-keyed when anything about the
+    // call changed, then what this call has to upload of them and -- check mode -- whether the host side kept its word
+    int keep_open()
+    {
+        for (int f = 0; f < AMT_F_COUNT; ++f) res_of[f] = -1;
+        for (int r = 0; r < NKEEP; ++r) res_hi[r] = (long)w.j_start - 2;
+        bool want[NKEEP];
         bool any_want = false;
-        for (int r = 0; r < HostWorkspace::NKEEP; ++r) {
+        for (int r = 0; r < NKEEP; ++r) {
             want[r] = keep_want[kKeepField[r]];
             any_want = any_want || want[r];
         }
         const int key[16] = {(int)sizeof(T), h.ims, h.ime, h.kms, h.kme, h.jms, h.jme, w.j_start, w.j_end, p.i0, p.i1, p.nk, p.k1, device, 0, 0};
         bool same = memcmp(res.key, key, sizeof key) == 0;
-        for (int r = 0; r < HostWorkspace::NKEEP && same; ++r)
-            same = want[r] == res.active[r] && (!want[r] || res.host[r] == items[kKeepField[r]].host);
+        for (int r = 0; r < NKEEP && same; ++r)
+            same = want[r] == res.active[r] && (!want[r] || res.host[r] == host[kKeepField[r]]);
         if (!same) {
             // another patch, another layout, other arrays or other settings: what only the device holds goes down to the
             // arrays it belongs to, then start over (nothing is in flight between calls)
-            rc = amt_keep_flush(ws);
+            const int rc = amt_keep_flush(ws);
             if (rc != AMT_OK) return rc;
             res.drop();
             memcpy(res.key, key, sizeof key);
-            res.esize = sizeof(T); res.idim = idim; res.kdim = kdim; res.i0 = p.i0; res.ni = (long)ni; res.k1 = p.k1; res.nk = p.nk;
+            res.cells = cells;
             res.j_start = w.j_start; res.j_end = w.j_end; res.jms = h.jms;
-            for (int r = 0; r < HostWorkspace::NKEEP; ++r) {
+            for (int r = 0; r < NKEEP; ++r) {
                 if (!want[r]) continue;
-                const size_t each = (kKeepRank[r] == 3 ? r3 * wrow : kKeepRank[r] == 2 ? r2 * wrow : n1) * sizeof(T);
+                const size_t each = (amt_keep_rank(r) == 3 ? r3 * pl.wrow : amt_keep_rank(r) == 2 ? r2 * pl.wrow : n1) * sizeof(T);
                 const hipError_t e = hipMalloc((void **)&res.buf[r], each);
                 if (e != hipSuccess) {
                     (void)hipGetLastError();
                     res.drop();
                     memset(res.key, 0, sizeof res.key);
                     return amt_fail(AMT_ERR_ALLOC, "kept arrays: hipMalloc of %zu bytes for %s failed (amt_host_cache_enable(0) / "
-                                    "amt_host_defer(NULL, 0) run without them)", each, kKeepName[r]);
+                                    "amt_host_defer(NULL, 0) run without them)", each, amt_keep_name(r));
                 }
                 res.bytes[r] = each;
                 res.active[r] = true;
-                res.host[r] = items[kKeepField[r]].host;
+                res.host[r] = host[kKeepField[r]];
             }
         }
-        for (int r = 0; r < HostWorkspace::NKEEP && any_want; ++r) {
+        for (int r = 0; r < NKEEP && any_want; ++r) {
             if (!res.active[r]) continue;
             const int f = kKeepField[r];
             res_of[f] = r;
             if (res.poisoned[r])
                 return amt_fail(AMT_ERR_PRECONDITION, "deferred output %s: an earlier call failed part-way and its device copy is undefined; "
                                 "call amt_host_invalidate for it (the host array, as last fetched, is the truth again) before the next sub-step",
-                                kKeepName[r]);
-            res_upload[r] = !res.valid[r] && items[f].in;
+                                amt_keep_name(r));
+            res_upload[r] = !res.valid[r] && kAmtField[f].in;
             if (!res.check) continue;
-            if (r < HostWorkspace::NCACHE) {
-                // debug mode: a cached array that changed on the host without amt_host_invalidate is an error.  The
-                // checksum covers exactly the rows a call uploads (rows j_start-1 / j_end+1 only for the halo arrays)
-                const int lo = items[f].halo ? w.j_start - 1 : w.j_start, hi = items[f].halo ? w.j_end + 1 : w.j_end;
-                const uint64_t now_sum = kKeepRank[r] == 3 ? amt_host_sum(items[f].host + (size_t)(lo - h.jms) * r3, (size_t)(hi - lo + 1) * r3 * sizeof(T))
-                                       : kKeepRank[r] == 2 ? amt_host_sum(items[f].host + (size_t)(w.j_start - 1 - h.jms) * r2, r2 * wrow * sizeof(T))
-                                                           : amt_host_sum(items[f].host, n1 * sizeof(T));
+            if (r < NCACHE) {
+                // debug mode: a cached array that changed on the host without amt_host_invalidate is an error
+                const uint64_t now_sum = uploaded_sum(f);
                 if (res.valid[r] && now_sum != res.sum[r]) {
                     res.valid[r] = false;
                     return amt_fail(AMT_ERR_PRECONDITION, "residency cache: %s changed on the host since it was uploaded "
-                                    "but amt_host_invalidate was not called for it (amt_host_cache_check)", kKeepName[r]);
+                                    "but amt_host_invalidate was not called for it (amt_host_cache_check)", amt_keep_name(r));
                 }
                 res.sum[r] = now_sum;
             } else if (res.stale[r] && !amt_keep_canary(res, r, false)) {
                 // debug mode: the host array of a deferred output was written while the device held the truth
                 return amt_fail(AMT_ERR_PRECONDITION, "deferred output %s was written on the host while its device copy was newer: "
                                 "call amt_host_invalidate for it (the host is the truth) or amt_host_fetch before writing "
-                                "(amt_host_cache_check)", kKeepName[r]);
+                                "(amt_host_cache_check)", amt_keep_name(r));
+            }
+        }
+        return AMT_OK;
+    }
+
+    // ---- stage: kept arrays, close.  What the device copies are worth after a call that ended with rc
+    void keep_close(int rc)
+    {
+        fail_guard.ok = (rc == AMT_OK);
+        for (int r = 0; r < NKEEP; ++r) {
+            if (!res.active[r]) continue;
+            if (r < NCACHE) {
+                res.valid[r] = (rc == AMT_OK);                // a cached input of a failed call simply goes up again
+            } else if (rc == AMT_OK) {
+                // the device copy is the truth from here on.  (After a call that FAILED once kernels were out, fail_guard marks the
+                // deferred copies undefined: amt_host_fetch / the next call refuse them until amt_host_invalidate.)
+                res.valid[r] = res.stale[r] = true;
+                if (res.check) amt_keep_canary(res, r, true);
             }
         }
     }
-    // A call that fails after its first kernel went out (any of the early returns below) leaves the deferred in/out copies
-    // (level 1 of ww, t, mu: advanced in place, chunk by chunk) partly a sub-step ahead: a retry would apply the sub-step twice
-    // to those rows and a fetch would bring a half-advanced state down.  They are marked undefined.
-    struct FailGuard {
-        HostWorkspace::Kept &k;
-        bool launched = false, ok = false;
-        ~FailGuard()
-        {
-            if (!launched || ok) return;
-            for (int r = HostWorkspace::NCACHE; r < HostWorkspace::NKEEP; ++r)
-                if (k.active[r] && (k.stale[r] || k.valid[r])) { k.valid[r] = k.stale[r] = false; k.poisoned[r] = true; }
-        }
-    } fail_guard{res};
-    // staging buffer: mirrors the arena from stage_base on
-    const size_t stage_base = pack_big ? 0 : small_begin;
-    char *stage = nullptr;
-    if (pack_small) {
-        const hipError_t e = ws.stage_reserve(arena_end - stage_base);
-        if (e == hipErrorOutOfMemory) return amt_fail(AMT_ERR_ALLOC, "hipHostMalloc of %zu bytes failed", arena_end - stage_base);
+
+    // ---- stage: the page-locked staging buffer of a packed call
+    int stage_open()
+    {
+        stage_base = pl.pack_big ? 0 : ar.small_begin;
+        if (!pl.pack_small) return AMT_OK;
+        const hipError_t e = ws.stage_reserve(ar.end - stage_base);
+        if (e == hipErrorOutOfMemory) return amt_fail(AMT_ERR_ALLOC, "hipHostMalloc of %zu bytes failed", ar.end - stage_base);
         AMT_HIP(e);
         stage = ws.stage;
-    }
-    auto staged = [&](const T *devptr) -> T * {               // the staging twin of a device address
-        return reinterpret_cast<T *>(stage + ((reinterpret_cast<const char *>(devptr) - ws.arena) - stage_base));
-    };
-    const double t_alloc = now();
-    const hipStream_t up = ws.up, comp = ws.comp, down = ws.down;
-
-    // ---- the 1-D and 2-D arrays, once -----------------------------------------------------------
-    for (int f = 0; f < 26; ++f) {
-        const Item &it = items[f];
-        if (it.rank == 3 || !it.in) continue;                 // muave, muts, mudf: outputs only
-        const size_t n = it.rank == 1 ? n1 : r2 * wrow;
-        const T *src = it.rank == 1 ? it.host : it.host + (size_t)(w.j_start - 1 - h.jms) * r2;
-        if (res_of[f] >= 0) {                                 // cached 2-D / 1-D input, deferred mu: up only while the device copy is not valid
-            if (res_upload[res_of[f]])
-                AMT_HIP(hipMemcpyAsync(res.buf[res_of[f]], src, n * sizeof(T), hipMemcpyHostToDevice, up));
-            continue;
-        }
-        if (pack_small) memcpy(staged(dev[0][f]), src, n * sizeof(T));
-        else AMT_HIP(hipMemcpyAsync(dev[0][f], src, n * sizeof(T), hipMemcpyHostToDevice, up));
-    }
-    if (pack_small && !pack_big)
-        AMT_HIP(hipMemcpyAsync(ws.arena + small_begin, stage, arena_end - small_begin, hipMemcpyHostToDevice, up));
-
-    // chunk c: rows c0..c1 of the window
-    auto chunk_rows = [&](int c, int &c0, int &c1) {
-        c0 = w.j_start + (int)(c * rows);
-        c1 = (c0 + rows - 1 < w.j_end) ? (int)(c0 + rows - 1) : w.j_end;
-    };
-    // chunk c's window cells of ww, t, t_ave: nothing else of the host arrays is touched
-    auto download = [&](int c) -> hipError_t {
-        const int s = c % nset;
-        int c0, c1;
-        chunk_rows(c, c0, c1);
-        hipError_t e = hipStreamWaitEvent(down, ws.computed[s], 0);
-        for (int f = 0; f < 26 && p.nk > 0 && e == hipSuccess; ++f) {
-            const Item &it = items[f];
-            if (!it.out || it.rank != 3 || res_of[f] >= 0) continue;   // deferred outputs stay on the device
-            hipMemcpy3DParms cp;
-            memset(&cp, 0, sizeof cp);
-            cp.srcPtr = make_hipPitchedPtr(dev[s][f], (size_t)idim * sizeof(T), (size_t)idim, (size_t)kdim);
-            cp.dstPtr = make_hipPitchedPtr(const_cast<T *>(it.host), (size_t)idim * sizeof(T), (size_t)idim, (size_t)kdim);
-            cp.srcPos = make_hipPos((size_t)p.i0 * sizeof(T), (size_t)p.k1, 1);
-            cp.dstPos = make_hipPos((size_t)p.i0 * sizeof(T), (size_t)p.k1, (size_t)(c0 - h.jms));
-            cp.extent = make_hipExtent(ni * sizeof(T), (size_t)p.nk, (size_t)(c1 - c0 + 1));
-            cp.kind = hipMemcpyDeviceToHost;
-            e = hipMemcpy3DAsync(&cp, down);
-        }
-        return e != hipSuccess ? e : hipEventRecord(ws.drained[s], down);
-    };
-
-    // download thread: takes chunks in order as the main thread reports them launched, reports
-    // them drained so that their buffer set can be reused
-    struct Downloader {
-        std::thread th;
-        std::mutex m;
-        std::condition_variable cv;
-        int launched = 0, drained = 0;
-        bool stop = false;
-        hipError_t err = hipSuccess;
-        ~Downloader()
-        {
-            { std::lock_guard<std::mutex> lk(m); stop = true; }
-            cv.notify_all();
-            if (th.joinable()) th.join();
-        }
-    } dl;
-    if (threaded) try {
-        dl.th = std::thread([&, device] {
-            hipError_t e = hipSetDevice(device);
-            for (int c = 0; c < nchunk; ++c) {
-                {
-                    std::unique_lock<std::mutex> lk(dl.m);
-                    dl.cv.wait(lk, [&] { return dl.stop || dl.launched > c; });
-                    if (dl.launched <= c) return;
-                }
-                if (e == hipSuccess) e = download(c);
-                if (e == hipSuccess) e = hipStreamSynchronize(down);
-                {
-                    std::lock_guard<std::mutex> lk(dl.m);
-                    if (e != hipSuccess) dl.err = e;
-                    dl.drained = c + 1;
-                }
-                dl.cv.notify_all();
-            }
-        });
-    } catch (const std::exception &) {
-        threaded = false;                                     // no thread to be had: the downloads are queued from this one (the pageable order)
+        return AMT_OK;
     }
 
-    // ---- the chunks -----------------------------------------------------------------------------
-    for (int c = 0; c < nchunk; ++c) {
-        const int s = c % nset;
-        int c0, c1;
-        chunk_rows(c, c0, c1);
-        const int ja = c0 - 1;                                // device row 0 <-> Fortran row ja
-        if (c >= nset) {                                      // set s is free again
-            if (threaded) {
-                std::unique_lock<std::mutex> lk(dl.m);
-                dl.cv.wait(lk, [&] { return dl.drained > c - nset; });
-                if (dl.err != hipSuccess) break;
-            } else {
-                AMT_HIP(hipStreamWaitEvent(up, ws.drained[s], 0));
-            }
-        }
-        for (int f = 0; f < 26; ++f) {
-            const Item &it = items[f];
-            if (it.rank != 3 || !it.in) continue;
-            if (f == F_WW) {                                  // level 1 only
-                const T *src = it.host + (size_t)(c0 - h.jms) * r3 + (size_t)p.k1 * idim;
-                if (res_of[f] >= 0) {                             // deferred: goes up only while the device copy is not valid
-                    if (res_upload[res_of[f]])
-                        AMT_HIP(hipMemcpy2DAsync(reinterpret_cast<T *>(res.buf[res_of[f]]) + (size_t)(c0 - (w.j_start - 1)) * r3 + (size_t)p.k1 * idim,
-                                                 r3 * sizeof(T), src, r3 * sizeof(T), (size_t)idim * sizeof(T), (size_t)(c1 - c0 + 1),
-                                                 hipMemcpyHostToDevice, up));
-                    continue;
-                }
-                T *dst = dev[s][f] + r3 + (size_t)p.k1 * idim;
-                if (pack_big)
-                    for (int j = c0; j <= c1; ++j)
-                        memcpy(staged(dst) + (size_t)(j - c0) * r3, src + (size_t)(j - c0) * r3, (size_t)idim * sizeof(T));
-                else
-                    AMT_HIP(hipMemcpy2DAsync(dst, r3 * sizeof(T), src, r3 * sizeof(T), (size_t)idim * sizeof(T),
-                                             (size_t)(c1 - c0 + 1), hipMemcpyHostToDevice, up));
+    // ---- stage: the 1-D and 2-D arrays go up, once
+    int upload_small()
+    {
+        for (int f = 0; f < AMT_F_COUNT; ++f) {
+            const int rank = amt_field_rank(f);
+            if (rank == 3 || !kAmtField[f].in) continue;      // muave, muts, mudf: outputs only
+            const size_t n = rank == 1 ? n1 : r2 * pl.wrow;
+            const T *src = rank == 1 ? host[f] : host[f] + (size_t)(w.j_start - 1 - h.jms) * r2;
+            if (res_of[f] >= 0) {                             // cached 2-D / 1-D input, deferred mu: up only while the device copy is not valid
+                if (res_upload[res_of[f]]) AMT_HIP(hipMemcpyAsync(kept(f), src, n * sizeof(T), hipMemcpyHostToDevice, ws.up));
                 continue;
             }
-            int lo = it.halo ? c0 - 1 : c0;
-            const int hi = it.halo ? c1 + 1 : c1;
+            if (pl.pack_small) memcpy(staged(dev[0][f]), src, n * sizeof(T));
+            else AMT_HIP(hipMemcpyAsync(dev[0][f], src, n * sizeof(T), hipMemcpyHostToDevice, ws.up));
+        }
+        if (pl.pack_small && !pl.pack_big)
+            AMT_HIP(hipMemcpyAsync(ws.arena + ar.small_begin, stage, ar.end - ar.small_begin, hipMemcpyHostToDevice, ws.up));
+        return AMT_OK;
+    }
+
+    // level 1 of rows c0..c1 of ww, the only part of it the routine reads
+    int upload_ww_level1(int s, int c0, int c1)
+    {
+        const int f = AMT_F_WW;
+        const T *src = host[f] + (size_t)(c0 - h.jms) * r3 + (size_t)p.k1 * p.idim;
+        const size_t pitch = r3 * sizeof(T), width = (size_t)p.idim * sizeof(T), nrow = (size_t)(c1 - c0 + 1);
+        if (res_of[f] >= 0) {                                 // deferred: goes up only while the device copy is not valid
+            if (res_upload[res_of[f]])
+                AMT_HIP(hipMemcpy2DAsync(kept(f) + (size_t)(c0 - (w.j_start - 1)) * r3 + (size_t)p.k1 * p.idim, pitch, src, pitch, width, nrow,
+                                         hipMemcpyHostToDevice, ws.up));
+            return AMT_OK;
+        }
+        T *dst = dev[s][f] + r3 + (size_t)p.k1 * p.idim;
+        if (pl.pack_big)
+            for (int j = c0; j <= c1; ++j) memcpy(staged(dst) + (size_t)(j - c0) * r3, src + (size_t)(j - c0) * r3, width);
+        else
+            AMT_HIP(hipMemcpy2DAsync(dst, pitch, src, pitch, width, nrow, hipMemcpyHostToDevice, ws.up));
+        return AMT_OK;
+    }
+
+    // ---- stage: upload of chunk c -- its rows, plus one halo row each side of the arrays the stencil reads across rows
+    int upload_chunk(int c)
+    {
+        const Chunk k = chunk(c);
+        const int s = k.s, c0 = k.c0, c1 = k.c1, ja = c0 - 1;  // device row 0 <-> Fortran row ja
+        for (int f = 0; f < AMT_F_COUNT; ++f) {
+            if (amt_field_rank(f) != 3 || !kAmtField[f].in) continue;
+            if (f == AMT_F_WW) {
+                if (int rc = upload_ww_level1(s, c0, c1)) return rc;
+                continue;
+            }
+            int lo = halo[f] ? c0 - 1 : c0;
+            const int hi = halo[f] ? c1 + 1 : c1;
             if (res_of[f] >= 0) {
                 // kept: its rows go up only while the device copy is not valid, and every row ONCE per call -- a later chunk
                 // starts behind what the earlier ones uploaded (its lower halo rows are already there, and the kernel of the
@@ -744,113 +734,151 @@ static int amt_host_call(const AmtArgs<T> &h)
                 if (res_upload[r]) {
                     if (lo <= res_hi[r]) lo = (int)res_hi[r] + 1;
                     if (lo <= hi)
-                        AMT_HIP(hipMemcpyAsync(reinterpret_cast<T *>(res.buf[r]) + (size_t)(lo - (w.j_start - 1)) * r3,
-                                               it.host + (size_t)(lo - h.jms) * r3, (size_t)(hi - lo + 1) * r3 * sizeof(T),
-                                               hipMemcpyHostToDevice, up));
+                        AMT_HIP(hipMemcpyAsync(kept(f) + (size_t)(lo - (w.j_start - 1)) * r3, host[f] + (size_t)(lo - h.jms) * r3,
+                                               (size_t)(hi - lo + 1) * r3 * sizeof(T), hipMemcpyHostToDevice, ws.up));
                     res_hi[r] = hi;
                 }
                 continue;
             }
             const size_t n = (size_t)(hi - lo + 1) * r3 * sizeof(T);
-            if (pack_big) memcpy(staged(dev[s][f]) + (size_t)(lo - ja) * r3, it.host + (size_t)(lo - h.jms) * r3, n);
-            else AMT_HIP(hipMemcpyAsync(dev[s][f] + (size_t)(lo - ja) * r3, it.host + (size_t)(lo - h.jms) * r3, n,
-                                        hipMemcpyHostToDevice, up));
+            if (pl.pack_big) memcpy(staged(dev[s][f]) + (size_t)(lo - ja) * r3, host[f] + (size_t)(lo - h.jms) * r3, n);
+            else AMT_HIP(hipMemcpyAsync(dev[s][f] + (size_t)(lo - ja) * r3, host[f] + (size_t)(lo - h.jms) * r3, n, hipMemcpyHostToDevice, ws.up));
         }
-        if (pack_big)                                         // one chunk: everything, small arrays included
-            AMT_HIP(hipMemcpyAsync(ws.arena, stage, arena_end, hipMemcpyHostToDevice, up));
-        AMT_HIP(hipEventRecord(ws.uploaded[s], up));
-        AmtArgs<T> d = h;
-        T *q[26];
-        for (int f = 0; f < 26; ++f)                          // every array as if it began at row ja
-            q[f] = items[f].rank == 2 ? (res_of[f] >= 0 ? reinterpret_cast<T *>(res.buf[res_of[f]]) : dev[0][f]) + (size_t)(ja - (w.j_start - 1)) * r2
-                 : items[f].rank == 1 ? (res_of[f] >= 0 ? reinterpret_cast<T *>(res.buf[res_of[f]]) : dev[0][f])
-                 : res_of[f] >= 0 ? reinterpret_cast<T *>(res.buf[res_of[f]]) + (size_t)(ja - (w.j_start - 1)) * r3 : dev[s][f];
-        d.ww = q[0]; d.ww_1 = q[1]; d.u = q[2]; d.u_1 = q[3]; d.v = q[4]; d.v_1 = q[5]; d.mu = q[6];
-        d.mut = q[7]; d.muave = q[8]; d.muts = q[9]; d.muu = q[10]; d.muv = q[11]; d.mudf = q[12];
-        d.t = q[13]; d.t_1 = q[14]; d.t_ave = q[15]; d.ft = q[16]; d.mu_tend = q[17];
-        d.dnw = q[18]; d.fnm = q[19]; d.fnp = q[20]; d.rdnw = q[21]; d.msfuy = q[22];
-        d.msfvx_inv = q[23]; d.msftx = q[24]; d.msfty = q[25];
-        d.jms = ja; d.jme = c1 + 1; d.jts = c0; d.jte = c1;  // a tile of the same domain (global jds, jde)
-        AMT_HIP(hipStreamWaitEvent(comp, ws.uploaded[s], 0));
-        fail_guard.launched = true;
-        rc = amt_device_call<T>(comp, AMT_VARIANT_AUTO, d);
-        if (rc == AMT_OK && getenv("AMT_TEST_FAIL_AFTER_LAUNCH"))   // test hook: a failure after the first kernel went out
-            rc = amt_fail(AMT_ERR_HIP, "AMT_TEST_FAIL_AFTER_LAUNCH: simulated failure after chunk %d was launched", c);
-        if (rc != AMT_OK) break;
-        AMT_HIP(hipEventRecord(ws.computed[s], comp));
-        if (threaded) {
-            { std::lock_guard<std::mutex> lk(dl.m); dl.launched = c + 1; }
-            dl.cv.notify_all();
-        } else if (!pack_big) {
-            AMT_HIP(download(c));
-        }
-    }
-    if (threaded) {                                           // all launched chunks drain, then the thread ends
-        { std::lock_guard<std::mutex> lk(dl.m); dl.stop = true; }
-        dl.cv.notify_all();
-        dl.th.join();
-        if (dl.err != hipSuccess && rc == AMT_OK)
-            rc = amt_fail(AMT_ERR_HIP, "download of a chunk failed: %s", hipGetErrorString(dl.err));
+        if (pl.pack_big)                                      // one chunk: everything, small arrays included
+            AMT_HIP(hipMemcpyAsync(ws.arena, stage, ar.end, hipMemcpyHostToDevice, ws.up));
+        AMT_HIP(hipEventRecord(ws.uploaded[s], ws.up));
+        return AMT_OK;
     }
 
-    // ---- the outputs that come down once, after the last kernel -----------------------------------
-    if (rc == AMT_OK) {
-        AMT_HIP(hipStreamWaitEvent(down, ws.computed[(nchunk - 1) % nset], 0));
-        if (pack_small) {
-            const size_t from = pack_big ? out3_begin : small_begin;
-            AMT_HIP(hipMemcpyAsync(stage + (from - stage_base), ws.arena + from, small_out_end - from,
-                                   hipMemcpyDeviceToHost, down));
-            AMT_HIP(hipStreamSynchronize(down));
-            for (int f = 0; f < 26; ++f) {                    // scatter: the window's cells only
-                const Item &it = items[f];
-                if (!it.out || res_of[f] >= 0) continue;      // deferred outputs stay on the device
-                if (it.rank == 2) {
-                    for (int j = w.j_start; j <= w.j_end; ++j)
-                        memcpy(const_cast<T *>(it.host) + (size_t)(j - h.jms) * r2 + p.i0,
-                               staged(dev[0][f]) + (size_t)(j - w.j_start + 1) * r2 + p.i0, ni * sizeof(T));
-                } else if (pack_big) {
-                    for (int j = w.j_start; j <= w.j_end; ++j)
-                        for (int k = 0; k < p.nk; ++k) {
-                            const size_t e = (size_t)(p.k1 + k) * idim + p.i0;
-                            memcpy(const_cast<T *>(it.host) + (size_t)(j - h.jms) * r3 + e,
-                                   staged(dev[0][f]) + (size_t)(j - w.j_start + 1) * r3 + e, ni * sizeof(T));
-                        }
-                }
-            }
-        } else {
-            for (int f = 0; f < 26; ++f) {
-                const Item &it = items[f];
-                if (!it.out || it.rank != 2 || res_of[f] >= 0) continue;
+    // ---- stage: launch of chunk c, as a tile of the same domain (global jds, jde) whose arrays all begin at row c0 - 1.
+    // Returns what the kernel call returned in `rc`; its own return value is that of the stream calls around it.
+    int launch_chunk(int c, int &rc)
+    {
+        const Chunk k = chunk(c);
+        const int s = k.s, c0 = k.c0, c1 = k.c1, ja = c0 - 1;
+        AmtArgs<T> d = h;
+        T *q[AMT_F_COUNT];
+        for (int f = 0; f < AMT_F_COUNT; ++f) {
+            const int rank = amt_field_rank(f);
+            const size_t row = rank == 3 ? r3 : r2;
+            q[f] = rank == 1 ? (res_of[f] >= 0 ? kept(f) : dev[0][f])
+                 : res_of[f] >= 0 ? kept(f) + (size_t)(ja - (w.j_start - 1)) * row
+                 : rank == 2 ? dev[0][f] + (size_t)(ja - (w.j_start - 1)) * row : dev[s][f];
+        }
+        amt_args_set_fields(d, q);
+        d.jms = ja; d.jme = c1 + 1; d.jts = c0; d.jte = c1;
+        AMT_HIP(hipStreamWaitEvent(ws.comp, ws.uploaded[s], 0));
+        fail_guard.launched = true;
+        rc = amt_device_call<T>(ws.comp, AMT_VARIANT_AUTO, d);
+        if (rc == AMT_OK && getenv("AMT_TEST_FAIL_AFTER_LAUNCH"))   // test hook: a failure after the first kernel went out
+            rc = amt_fail(AMT_ERR_HIP, "AMT_TEST_FAIL_AFTER_LAUNCH: simulated failure after chunk %d was launched", c);
+        if (rc == AMT_OK) AMT_HIP(hipEventRecord(ws.computed[s], ws.comp));
+        return AMT_OK;
+    }
+
+    // ---- stage: download of chunk c -- its window cells of ww, t, t_ave: nothing else of the host arrays is touched
+    hipError_t download_chunk(int c)
+    {
+        const Chunk k = chunk(c);
+        hipError_t e = hipStreamWaitEvent(ws.down, ws.computed[k.s], 0);
+        for (int f = 0; f < AMT_F_COUNT && p.nk > 0 && e == hipSuccess; ++f) {
+            if (!kAmtField[f].out || amt_field_rank(f) != 3 || res_of[f] >= 0) continue;   // deferred outputs stay on the device
+            e = amt_window_down(cells, 3, const_cast<T *>(host[f]), (size_t)(k.c0 - h.jms), dev[k.s][f], 1, (size_t)(k.c1 - k.c0 + 1), ws.down);
+        }
+        return e != hipSuccess ? e : hipEventRecord(ws.drained[k.s], ws.down);
+    }
+
+    // ---- stage: the outputs that come down once, after the last kernel
+    int download_small()
+    {
+        AMT_HIP(hipStreamWaitEvent(ws.down, ws.computed[(pl.nchunk - 1) % pl.nset], 0));
+        if (!pl.pack_small) {
+            for (int f = 0; f < AMT_F_COUNT; ++f) {
+                if (!kAmtField[f].out || amt_field_rank(f) != 2 || res_of[f] >= 0) continue;
                 // the window's cells only (a strided copy): two host threads running tiles that split i
                 // must not rewrite each other's columns with what they uploaded
-                AMT_HIP(hipMemcpy2DAsync(const_cast<T *>(it.host) + (size_t)(w.j_start - h.jms) * r2 + p.i0, r2 * sizeof(T),
-                                         dev[0][f] + r2 + p.i0, r2 * sizeof(T), ni * sizeof(T), (size_t)nj,
-                                         hipMemcpyDeviceToHost, down));
+                AMT_HIP(amt_window_down(cells, 2, const_cast<T *>(host[f]), (size_t)(w.j_start - h.jms), dev[0][f], 1, (size_t)nj, ws.down));
+            }
+            return AMT_OK;
+        }
+        const size_t from = pl.pack_big ? ar.out3_begin : ar.small_begin;
+        AMT_HIP(hipMemcpyAsync(stage + (from - stage_base), ws.arena + from, ar.small_out_end - from, hipMemcpyDeviceToHost, ws.down));
+        AMT_HIP(hipStreamSynchronize(ws.down));
+        for (int f = 0; f < AMT_F_COUNT; ++f) {               // scatter: the window's cells only
+            if (!kAmtField[f].out || res_of[f] >= 0) continue;   // deferred outputs stay on the device
+            T *to = const_cast<T *>(host[f]);
+            if (amt_field_rank(f) == 2) {
+                for (int j = w.j_start; j <= w.j_end; ++j)
+                    memcpy(to + (size_t)(j - h.jms) * r2 + p.i0, staged(dev[0][f]) + (size_t)(j - w.j_start + 1) * r2 + p.i0, ni * sizeof(T));
+            } else if (pl.pack_big) {
+                for (int j = w.j_start; j <= w.j_end; ++j)
+                    for (int k = 0; k < p.nk; ++k) {
+                        const size_t e = (size_t)(p.k1 + k) * p.idim + p.i0;
+                        memcpy(to + (size_t)(j - h.jms) * r3 + e, staged(dev[0][f]) + (size_t)(j - w.j_start + 1) * r3 + e, ni * sizeof(T));
+                    }
             }
         }
+        return AMT_OK;
     }
-    const double t_enq = now();
-    for (hipStream_t st : {up, comp, down}) {
+};
+}  // namespace
+
+template <typename T>
+static int amt_host_call(const AmtArgs<T> &h)
+{
+    Oneshot<T> o(h);
+    bool empty = false;
+    int rc = amt_build_params(h, o.p, o.w, &empty);
+    if (rc != AMT_OK || empty) return rc;
+    int ndev = 0;
+    AMT_HIP(hipGetDeviceCount(&ndev));
+    if (ndev < 1) return amt_fail(AMT_ERR_NO_DEVICE, "no HIP device visible");
+    AMT_HIP(hipGetDevice(&o.device));
+    o.describe();
+    const Plan &pl = o.pl;
+    const bool trace = getenv("AMT_STREAM_TRACE") != nullptr;
+    const double t_begin = now_ms();
+
+    if ((rc = o.acquire()) != AMT_OK) return rc;
+    WorkspaceScope scope{o.ws};                               // drains the three streams on every way out
+    if ((rc = o.keep_open()) != AMT_OK) return rc;
+    if ((rc = o.stage_open()) != AMT_OK) return rc;
+    const double t_alloc = now_ms();
+    if ((rc = o.upload_small()) != AMT_OK) return rc;
+
+    Downloader dl;                                            // pageable 3-D arrays, several chunks: the downloads are issued by a second thread
+    const bool threaded = pl.may_thread && pl.nchunk > 1 &&   // (none to be had: they are queued from this one, the pageable order)
+                          dl.start(o.device, pl.nchunk, [&o](int c) {
+                              const hipError_t e = o.download_chunk(c);
+                              return e != hipSuccess ? e : hipStreamSynchronize(o.ws.down);
+                          });
+    for (int c = 0; c < pl.nchunk; ++c) {
+        if (c >= pl.nset) {                                   // buffer set c % nset is free again
+            if (threaded) { if (!dl.wait_drained(c - pl.nset)) break; }
+            else AMT_HIP(hipStreamWaitEvent(o.ws.up, o.ws.drained[c % pl.nset], 0));
+        }
+        if (int e = o.upload_chunk(c)) return e;
+        if (int e = o.launch_chunk(c, rc)) return e;
+        if (rc != AMT_OK) break;
+        if (threaded) dl.launched(c);
+        else if (!pl.pack_big) AMT_HIP(o.download_chunk(c));
+    }
+    if (threaded && dl.finish() != hipSuccess && rc == AMT_OK)
+        rc = amt_fail(AMT_ERR_HIP, "download of a chunk failed: %s", hipGetErrorString(dl.err));
+    if (rc == AMT_OK)
+        if (int e = o.download_small()) return e;
+
+    const double t_enq = now_ms();
+    for (hipStream_t st : {o.ws.up, o.ws.comp, o.ws.down}) {
         hipError_t e = hipStreamSynchronize(st);
         if (e != hipSuccess && rc == AMT_OK)
             rc = amt_fail(AMT_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
     }
-    fail_guard.ok = (rc == AMT_OK);
-    for (int r = 0; r < HostWorkspace::NKEEP; ++r) {
-        if (!res.active[r]) continue;
-        if (r < HostWorkspace::NCACHE) {
-            res.valid[r] = (rc == AMT_OK);                    // a cached input of a failed call simply goes up again
-        } else if (rc == AMT_OK) {
-            // the device copy is the truth from here on.  (After a call that FAILED once kernels were out, fail_guard marks the
-            // deferred copies undefined: amt_host_fetch / the next call refuse them until amt_host_invalidate.)
-            res.valid[r] = res.stale[r] = true;
-            if (res.check) amt_keep_canary(res, r, true);
-        }
-    }
+    o.keep_close(rc);
     if (trace)
         fprintf(stderr, "amt one-shot: %d chunk(s) of %ld rows, 3-D %s%s, small arrays %s; alloc %.2f ms, enqueue %.2f ms, drain %.2f ms\n",
-                nchunk, rows, pinned ? "pinned" : pack_big ? "packed" : "pageable", threaded ? " + download thread" : "",
-                pinned_small ? "pinned" : pack_small ? "packed" : "pageable", t_alloc - t_begin, t_enq - t_alloc, now() - t_enq);
+                pl.nchunk, pl.rows, o.pinned ? "pinned" : pl.pack_big ? "packed" : "pageable", threaded ? " + download thread" : "",
+                o.pinned_small ? "pinned" : pl.pack_small ? "packed" : "pageable", t_alloc - t_begin, t_enq - t_alloc, now_ms() - t_enq);
     return rc;
 }
 
