@@ -37,7 +37,8 @@
  *    82-85).  amt_last_error() gives the text for the calling thread.
  *  - Outputs outside the compute window, and level k = kte, keep the caller's
  *    contents (the reference uploads its OUT arrays for the same reason,
- *    advance_mu_t_no_async.cu:259,270-272).
+ *    advance_mu_t_no_async.cu:259,270-272).  Section (12) advances the ring a
+ *    specified / nested domain's window leaves out.
  *  - Calls on the same stream/handle are not re-entrant; different streams are
  *    independent.
  *
@@ -803,6 +804,64 @@ int amt_slab_halo_wait(amt_slab *slab);
 int amt_slab_step_end(amt_slab *slab);
 int amt_slab_halo_pack(amt_slab *slab);
 int amt_slab_halo_unpack(amt_slab *slab);
+
+/* ------------------------------------------------------------------------
+ * (12) Specified and nested lateral boundaries: the boundary-zone update on the device.  With `specified` or `nested` the
+ *      routine clips its compute window by one cell at every domain edge (module_small_step_em.f90:97-106; with periodic_x
+ *      in j only) and leaves t, mu and muts of that ring as the caller passed them.  In WRF's acoustic loop the ring is not
+ *      constant: after every advance_mu_t call three spec_bdyupdate calls of zone width 1 advance it with the boundary
+ *      tendencies.  These calls do the same.  With ihi = min(ite, ide-1), jhi = min(jte, jde-1), the BOUNDARY ZONE of a tile
+ *      is every cell (i, j), its <= i <= ihi, jts <= j <= jhi, that is not in the window of amt_compute_window; in it, each
+ *      cell exactly once,
+ *        t(i,k,j)  = t(i,k,j)  + dts * ft(i,k,j)        k = kts .. kte-1
+ *        mu(i,j)   = mu(i,j)   + dts * mu_tend(i,j)
+ *        muts(i,j) = muts(i,j) + dts * mu_tend(i,j)
+ *      each assignment two roundings in the arrays' type (product, then sum; no fused multiply-add; for fp32 dts is rounded
+ *      to float first, as the sweep does).  Bit-unchanged: everything outside the zone (NaN payloads included), level kte of
+ *      t, the zone's cells of ww, t_ave, muave and mudf, every input.  The sweep neither reads nor writes the zone's cells of
+ *      t, mu and muts (it reads t_1 across the edge), so the update commutes with it; it is enqueued behind it, where WRF has it.
+ *      periodic_x with specified: rows only, over the tile's whole width.  A tile that touches no domain edge: nothing to
+ *      do, AMT_OK, nothing enqueued.  A corner tile: the corner cell belongs to the row strip and is updated once.  A domain
+ *      so small that the window is empty (ide-ids < 3 or jde-jds < 3): the whole tile.  One launch does a whole update, for
+ *      every member of an ensemble.
+ *      AMT_ERR_PRECONDITION: neither specified nor nested (no zone to own); a tile outside memory; more than 65535 members
+ *      (one launch carries the member in a grid dimension).  AMT_ERR_INVALID_ARG:
+ *      members < 1, a NULL array.  All are reported before any device call, with or without a device.
+ *      NOT provided: the one-shot host-array calls of (1).  A host that owns the arrays owns the ring as well and does its
+ *      own boundary update.
+ * ------------------------------------------------------------------------ */
+/* pointer level, beside amt_advance_mu_t_device_* (members = 1) or amt_advance_mu_t_ensemble_device_* (member-stacked
+ * arrays); asynchronous on hip_stream (NULL = the default stream) */
+int amt_spec_bdy_update_device_f32(
+    void *hip_stream, int members,
+    float *t, const float *ft, float *mu, float *muts, const float *mu_tend, float dts,
+    int periodic_x, int specified, int nested,
+    int ids, int ide, int jds, int jde, int kde,
+    int ims, int ime, int jms, int jme, int kms, int kme,
+    int its, int ite, int jts, int jte, int kts, int kte);
+int amt_spec_bdy_update_device_f64(
+    void *hip_stream, int members,
+    double *t, const double *ft, double *mu, double *muts, const double *mu_tend, double dts,
+    int periodic_x, int specified, int nested,
+    int ids, int ide, int jds, int jde, int kde,
+    int ims, int ime, int jms, int jme, int kms, int kme,
+    int its, int ite, int jts, int jte, int kts, int kte);
+/* one update now, with the handle's dts (amt_domain_set_scalars); asynchronous on the handle's stream (wrapped handles: the
+ * caller's stream) */
+int amt_domain_spec_bdy_update(amt_domain *d);
+/* on = 0: off (the default; the step paths enqueue exactly what they do without this section).  Otherwise every sweep of
+ * amt_domain_step / amt_domain_step_timed is followed by one update on the same stream.  A handle keeps the setting under
+ * amt_slab_* and amt_grid_*: every sweep of amt_slab_step / amt_grid_step / *_step_timed and of amt_slab_step_end /
+ * amt_grid_step_end (a patch without a neighbour included) is followed by the update of that rank's own tile, on the domain's
+ * stream where the sweep's work has joined it -- every schedule, AMT_SLAB_NO_OVERLAP included.  Nothing is exchanged for it
+ * (the zone holds outputs only) and a rank whose patch touches no domain edge enqueues nothing.  A combination the handle
+ * does not admit is refused here and changes nothing. */
+int amt_domain_set_spec_bdy(amt_domain *d, int on);
+int amt_domain_spec_bdy(const amt_domain *d);                      /* the setting; 0 for NULL */
+/* the same for an ensemble: all members in one launch */
+int amt_ensemble_spec_bdy_update(amt_ensemble *e);
+int amt_ensemble_set_spec_bdy(amt_ensemble *e, int on);
+int amt_ensemble_spec_bdy(const amt_ensemble *e);
 
 #ifdef __cplusplus
 }

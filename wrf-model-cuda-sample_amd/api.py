@@ -123,6 +123,36 @@ def cyclic_fill(u, u_1, v, v_1, t_1, muu, muv, msfuy, msfvx_inv, config_flags,
     _lib.check(status)
 
 
+def spec_bdy_update(t, ft, mu, muts, mu_tend, dts, config_flags,
+                    ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,
+                    its, ite, jts, jte, kts, kte, *, members=1, stream=None):
+    """The boundary-zone update of a specified / nested patch's (``members`` > 1: a member-stacked ensemble's) torch device
+    tensors in place (``amt_spec_bdy_update_device_f32/_f64``, header section 12): ``t += dts*ft`` (levels kts..kte-1),
+    ``mu += dts*mu_tend``, ``muts += dts*mu_tend`` over the tile's cells outside the compute window.  Asynchronous on
+    ``stream`` (default: torch's current).  Call it behind ``advance_mu_t`` on the same stream."""
+    import torch
+    L = _lib.load_library()
+    arrays = (t, ft, mu, muts, mu_tend)
+    idim, kdim, jdim = ime - ims + 1, kme - kms + 1, jme - jms + 1
+    want = [jdim * kdim * idim] * 2 + [jdim * idim] * 3
+    dt = t.dtype if _is_torch(t) else None
+    if dt not in (torch.float32, torch.float64):
+        raise TypeError(f"unsupported dtype {dt}")
+    for a, n in zip(arrays, want):
+        if not (_is_torch(a) and a.is_cuda and a.dtype == dt and a.is_contiguous() and a.numel() == n * int(members)):
+            raise TypeError("spec_bdy_update needs contiguous CUDA tensors of one dtype and of the memory extents")
+    if stream is None:
+        stream = torch.cuda.current_stream(t.device)
+    handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+    real = ctypes.c_float if dt == torch.float32 else ctypes.c_double
+    fn = L.amt_spec_bdy_update_device_f32 if dt == torch.float32 else L.amt_spec_bdy_update_device_f64
+    with torch.cuda.device(t.device):
+        status = fn(ctypes.c_void_p(handle), int(members), *[ctypes.c_void_p(a.data_ptr()) for a in arrays], real(float(dts)),
+                    *flags_as_ints(config_flags),
+                    *[int(x) for x in (ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte)])
+    _lib.check(status)
+
+
 def advance_mu_t(ww, ww_1, u, u_1, v, v_1, mu, mut, muave, muts, muu, muv, mudf, t, t_1,
                  t_ave, ft, mu_tend, rdx, rdy, dts, epssm, dnw, fnm, fnp, rdnw,
                  msfuy, msfvx_inv, msftx, msfty, config_flags,

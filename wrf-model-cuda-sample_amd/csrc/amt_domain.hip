@@ -325,6 +325,8 @@ static int amt_domain_step_t(amt_domain *d, int n_sweeps)
         // cyclic boundaries: the wrap cells are refreshed in front of every sweep, on the same stream (the inputs are final there)
         int rc = d->cyclic ? amt_cyclic_refresh_domain("amt_domain_step", d, d->cyclic, 1) : AMT_OK;
         if (rc == AMT_OK) rc = amt_device_call<T>(d->stream, d->variant, a);
+        // specified / nested boundaries: the boundary zone is advanced behind the sweep, where WRF has its spec_bdyupdate calls
+        if (rc == AMT_OK && d->spec_bdy) rc = amt_bdy_update_domain("amt_domain_step", d, 1);
         if (rc == AMT_OK && d->guard_every) rc = amt_diag_after_sweep("amt_domain_step", d, 1);
         if (rc) return rc;
     }
@@ -347,6 +349,24 @@ extern "C" int amt_domain_set_cyclic(amt_domain *d, int axes)
 }
 
 extern "C" int amt_domain_cyclic(const amt_domain *d) { return d ? d->cyclic : 0; }
+
+extern "C" int amt_domain_spec_bdy_update(amt_domain *d)
+{
+    if (!d) return amt_fail(AMT_ERR_INVALID_ARG, "null domain");
+    DeviceScope scope(d->device);
+    return amt_bdy_update_domain("amt_domain_spec_bdy_update", d, 1);
+}
+
+extern "C" int amt_domain_set_spec_bdy(amt_domain *d, int on)
+{
+    if (!d) return amt_fail(AMT_ERR_INVALID_ARG, "null domain");
+    if (!on) { d->spec_bdy = 0; return AMT_OK; }
+    const int rc = amt_bdy_check_domain("amt_domain_set_spec_bdy", d, 1);
+    if (rc == AMT_OK) d->spec_bdy = 1;
+    return rc;
+}
+
+extern "C" int amt_domain_spec_bdy(const amt_domain *d) { return d ? d->spec_bdy : 0; }
 
 extern "C" int amt_domain_step(amt_domain *d, int n_sweeps)
 {
@@ -382,11 +402,12 @@ static int amt_domain_tune(amt_domain *d, int tries, float *ms_per_try, bool pre
 {
     DeviceScope scope(d->device);
     // the timed sweeps are scaffolding: an armed non-finite guard neither checks nor counts them (and does not stretch them)
-    struct GuardPause {
+    // nor does the boundary-zone update follow them
+    struct StepExtrasPause {
         amt_domain *d;
-        int every;
-        explicit GuardPause(amt_domain *dom) : d(dom), every(dom->guard_every) { d->guard_every = 0; }
-        ~GuardPause() { d->guard_every = every; }
+        int every, spec_bdy;
+        explicit StepExtrasPause(amt_domain *dom) : d(dom), every(dom->guard_every), spec_bdy(dom->spec_bdy) { d->guard_every = 0; d->spec_bdy = 0; }
+        ~StepExtrasPause() { d->guard_every = every; d->spec_bdy = spec_bdy; }
     } pause(d);
     auto bytes = [&](int f) { return d->count(f) * (size_t)d->dtype_bytes; };
     auto time_current = [&](float *ms) -> int {

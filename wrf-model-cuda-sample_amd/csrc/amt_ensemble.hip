@@ -176,6 +176,8 @@ static int amt_ensemble_step_t(amt_ensemble *e, int n_sweeps)
         // cyclic boundaries: every member's wrap cells in one launch in front of the sweep, on the same stream
         int rc = e->d.cyclic ? amt_cyclic_refresh_domain("amt_ensemble_step", &e->d, e->d.cyclic, e->members) : AMT_OK;
         if (rc == AMT_OK) rc = amt_device_call_ensemble<T>(e->d.stream, e->d.variant, e->members, a);
+        // specified / nested boundaries: every member's boundary zone in one launch behind the sweep
+        if (rc == AMT_OK && e->d.spec_bdy) rc = amt_bdy_update_domain("amt_ensemble_step", &e->d, e->members);
         if (rc == AMT_OK && e->d.guard_every) rc = amt_diag_after_sweep("amt_ensemble_step", &e->d, e->members);
         if (rc) return rc;
     }
@@ -198,6 +200,24 @@ extern "C" int amt_ensemble_set_cyclic(amt_ensemble *e, int axes)
 }
 
 extern "C" int amt_ensemble_cyclic(const amt_ensemble *e) { return e ? e->d.cyclic : 0; }
+
+extern "C" int amt_ensemble_spec_bdy_update(amt_ensemble *e)
+{
+    if (!e) return amt_fail(AMT_ERR_INVALID_ARG, "null ensemble");
+    DeviceScope scope(e->d.device);
+    return amt_bdy_update_domain("amt_ensemble_spec_bdy_update", &e->d, e->members);
+}
+
+extern "C" int amt_ensemble_set_spec_bdy(amt_ensemble *e, int on)
+{
+    if (!e) return amt_fail(AMT_ERR_INVALID_ARG, "null ensemble");
+    if (!on) { e->d.spec_bdy = 0; return AMT_OK; }
+    const int rc = amt_bdy_check_domain("amt_ensemble_set_spec_bdy", &e->d, e->members);
+    if (rc == AMT_OK) e->d.spec_bdy = 1;
+    return rc;
+}
+
+extern "C" int amt_ensemble_spec_bdy(const amt_ensemble *e) { return e ? e->d.spec_bdy : 0; }
 
 extern "C" int amt_ensemble_step(amt_ensemble *e, int n_sweeps)
 {

@@ -146,6 +146,11 @@ int grid_tile(amt_grid *g, hipStream_t stream, int its, int ite, int jts, int jt
     return beside_the_exchange ? amt_device_call_shared<T>(stream, g->dom->variant, a) : amt_device_call<T>(stream, g->dom->variant, a);
 }
 
+// Specified / nested boundaries (amt_domain_set_spec_bdy): the boundary-zone update of this rank's own
+// tile, on the domain's stream where the sweep's work has joined it.  The zone holds outputs only: nothing is exchanged for it,
+// and a patch that touches no domain edge enqueues nothing.
+int grid_bdy(amt_grid *g, const char *who) { return g->dom->spec_bdy ? amt_bdy_update_domain(who, g->dom, 1) : AMT_OK; }
+
 // the cells that read a neighbour's data, after the halos are in: boundary rows over the patch's whole width (they own the
 // corners), boundary columns over the rows in between; every tile is clipped on its own by the routine's window rule
 template <typename T>
@@ -236,6 +241,7 @@ int grid_step_t(amt_grid *g, int n_sweeps)
         }
         if (none) {                                                        // a world of one: the plain launch
             rc = grid_tile<T>(g, d->stream, ilo, ihi, jlo, jhi);
+            if (rc == AMT_OK) rc = grid_bdy(g, "amt_grid_step");
             if (rc) return rc;
             continue;
         }
@@ -247,6 +253,7 @@ int grid_step_t(amt_grid *g, int n_sweeps)
             if (rc == AMT_OK) rc = grid_unpack(g, d->stream);
             if (rc == AMT_OK) rc = grid_tile<T>(g, d->stream, ilo, ihi, jlo, jhi);
             if (rc == AMT_OK) rc = amt_exchange_enqueue_release(g->xchg, d->stream);
+            if (rc == AMT_OK) rc = grid_bdy(g, "amt_grid_step");
             if (rc) return rc;
             continue;
         }
@@ -273,6 +280,7 @@ int grid_step_t(amt_grid *g, int n_sweeps)
             if (rc == AMT_OK) rc = grid_edges<T>(g, g->comm_stream, lo, hi, lf, rt, unclipped, in_jlo, in_jhi);
             if (rc == AMT_OK) rc = amt_exchange_enqueue_release(g->xchg, g->comm_stream);
             join();                                                        // also after an error: the streams never stay apart
+            if (rc == AMT_OK) rc = grid_bdy(g, "amt_grid_step");           // behind the join: on the domain's stream
             if (rc) return rc;
             continue;
         }
@@ -295,6 +303,7 @@ int grid_step_t(amt_grid *g, int n_sweeps)
         // have pulled them)
         if (rc == AMT_OK) rc = amt_exchange_enqueue_release(g->xchg, g->comm_stream);
         join();
+        if (rc == AMT_OK) rc = grid_bdy(g, "amt_grid_step");
         if (rc) return rc;
     }
     return AMT_OK;
@@ -477,14 +486,15 @@ template <typename T>
 int external_end_t(amt_grid *g)
 {
     amt_domain *d = g->dom;
-    if (g->n_msg == 0) return AMT_OK;
+    if (g->n_msg == 0) return grid_bdy(g, "amt_grid_step_end");           // begin was the plain launch
     const EdgeCells ec = edge_cells(g);
     const bool lo = g->below >= 0, hi = g->above >= 0, lf = g->left >= 0, rt = g->right >= 0;
     if (!g->overlap) {
         int rc = external_move(g, d->stream, true);
         if (rc) return rc;
         AMT_HIP(hipEventRecord(g->unpacked, d->stream));
-        return grid_tile<T>(g, d->stream, ec.ilo, ec.ihi, ec.jlo, ec.jhi);
+        rc = grid_tile<T>(g, d->stream, ec.ilo, ec.ihi, ec.jlo, ec.jhi);
+        return rc ? rc : grid_bdy(g, "amt_grid_step_end");
     }
     const AmtWindow wclip = amt_window(d->periodic_x, d->specified, d->nested, d->ids, d->ide, d->jds, d->jde,
                                        ec.ilo, ec.ihi, ec.jlo, ec.jhi, d->kts, d->kte);
@@ -496,7 +506,7 @@ int external_end_t(amt_grid *g)
     if (rc == AMT_OK) rc = grid_edges<T>(g, g->comm_stream, lo, hi, lf, rt, unclipped, ec.jlo + (lo ? 1 : 0), ec.jhi - (hi ? 1 : 0));
     (void)hipEventRecord(g->edges_done, g->comm_stream);                   // also after an error: the streams never stay apart
     (void)hipStreamWaitEvent(d->stream, g->edges_done, 0);
-    return rc;
+    return rc ? rc : grid_bdy(g, "amt_grid_step_end");                    // behind the join: on the domain's stream
 }
 
 int external_begin(amt_grid *g)

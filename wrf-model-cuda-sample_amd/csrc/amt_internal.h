@@ -185,6 +185,7 @@ struct amt_domain {
     bool owns_fields = true;      // false: the arrays belong to the caller (amt_domain_wrap)
     bool owns_stream = true;      // false: the stream belongs to the caller
     int cyclic = 0;               // amt_cyclic_axes refreshed in front of every sweep (amt_domain_set_cyclic); 0 = off
+    int spec_bdy = 0;             // 1: the boundary-zone update follows every sweep (amt_domain_set_spec_bdy); 0 = off
     int placement_tries = 0;      // allocations of the state that were timed (amt_domain_create / amt_domain_tune_placement)
     float placement_ms[16] = {};  // sweep time on each (0: not tried)
     int guard_every = 0;          // non-finite guard: check after every n-th sweep (amt_domain_set_guard); 0 = off
@@ -222,6 +223,14 @@ inline void amt_domain_args(amt_domain *d, AmtArgs<T> &a)
 // ---------------------------------------------------------------------------
 int amt_cyclic_refresh_domain(const char *who, amt_domain *d, int axes, int members);
 int amt_cyclic_check_domain(const char *who, const amt_domain *d, int axes, int members);
+
+// ---------------------------------------------------------------------------
+// specified / nested lateral boundaries (amt_bdy.hip, header section 12): one boundary-zone update of `members`
+// member-stacked patches of the domain's shape on the domain's stream, with the domain's dts, and the argument /
+// precondition checks alone (host arithmetic).  An empty zone enqueues nothing.
+// ---------------------------------------------------------------------------
+int amt_bdy_update_domain(const char *who, amt_domain *d, int members);
+int amt_bdy_check_domain(const char *who, const amt_domain *d, int members);
 
 // ---------------------------------------------------------------------------
 // field statistics, comparison and the non-finite guard (amt_diag.hip, header section 10).  The steppers call these only

@@ -198,6 +198,18 @@ class Ensemble(_lib.HandleDiag):
         """``amt_ensemble_cyclic_fill``: one refresh of every member now, asynchronous on the handle's stream."""
         _lib.check(self.L.amt_ensemble_cyclic_fill(self.handle, int(axes)))
 
+    def set_spec_bdy(self, on: bool = True) -> None:
+        """``amt_ensemble_set_spec_bdy``: every sweep of ``step`` / ``step_timed`` is then followed by one launch that advances the
+        boundary zone of every member (specified / nested domains, header section 12).  False = off."""
+        _lib.check(self.L.amt_ensemble_set_spec_bdy(self.handle, int(bool(on))))
+
+    def spec_bdy(self) -> bool:
+        return bool(self.L.amt_ensemble_spec_bdy(self.handle))
+
+    def spec_bdy_update(self) -> None:
+        """``amt_ensemble_spec_bdy_update``: one update of every member now, asynchronous on the handle's stream."""
+        _lib.check(self.L.amt_ensemble_spec_bdy_update(self.handle))
+
     def sync(self) -> None:
         self._check(self.L.amt_ensemble_sync(self.handle))
 

@@ -761,6 +761,71 @@ MODULE amt_c_binding
          type(amt_guard_report), intent(inout) :: out
          integer(c_int) :: rc
       end function
+      ! (12) specified / nested lateral boundaries: the boundary-zone update t += dts*ft, mu += dts*mu_tend, muts += dts*mu_tend
+      ! over the tile's cells outside the compute window (WRF: three spec_bdyupdate calls behind every advance_mu_t call).
+      ! Pointer level (members = 1 for a single patch), asynchronous on hip_stream
+      function amt_spec_bdy_update_device_f32(hip_stream, members, t, ft, mu, muts, mu_tend, dts,                          &
+                                              periodic_x, specified, nested,                                            &
+                                              ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,                    &
+                                              its, ite, jts, jte, kts, kte) bind(C, name="amt_spec_bdy_update_device_f32") result(rc)
+         import :: c_ptr, c_int, c_float
+         type(c_ptr), value :: hip_stream
+         integer(c_int), value :: members
+         type(c_ptr), value :: t, ft, mu, muts, mu_tend                              ! device pointers
+         real(c_float), value :: dts
+         integer(c_int), value :: periodic_x, specified, nested
+         integer(c_int), value :: ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme
+         integer(c_int), value :: its, ite, jts, jte, kts, kte
+         integer(c_int) :: rc
+      end function
+      function amt_spec_bdy_update_device_f64(hip_stream, members, t, ft, mu, muts, mu_tend, dts,                          &
+                                              periodic_x, specified, nested,                                            &
+                                              ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,                    &
+                                              its, ite, jts, jte, kts, kte) bind(C, name="amt_spec_bdy_update_device_f64") result(rc)
+         import :: c_ptr, c_int, c_double
+         type(c_ptr), value :: hip_stream
+         integer(c_int), value :: members
+         type(c_ptr), value :: t, ft, mu, muts, mu_tend                              ! device pointers
+         real(c_double), value :: dts
+         integer(c_int), value :: periodic_x, specified, nested
+         integer(c_int), value :: ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme
+         integer(c_int), value :: its, ite, jts, jte, kts, kte
+         integer(c_int) :: rc
+      end function
+      ! one update now on the handle's stream; set: 1 = every sweep of the handle's stepping (amt_domain_step, amt_slab_step,
+      ! amt_grid_step, amt_*_step_end ...) is followed by one, 0 = off (the default)
+      function amt_domain_spec_bdy_update(handle) bind(C, name="amt_domain_spec_bdy_update") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int) :: rc
+      end function
+      function amt_domain_set_spec_bdy(handle, on) bind(C, name="amt_domain_set_spec_bdy") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: on
+         integer(c_int) :: rc
+      end function
+      function amt_domain_spec_bdy(handle) bind(C, name="amt_domain_spec_bdy") result(on)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int) :: on
+      end function
+      function amt_ensemble_spec_bdy_update(handle) bind(C, name="amt_ensemble_spec_bdy_update") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_set_spec_bdy(handle, on) bind(C, name="amt_ensemble_set_spec_bdy") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: on
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_spec_bdy(handle) bind(C, name="amt_ensemble_spec_bdy") result(on)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int) :: on
+      end function
    end interface
 
    ! enum amt_field (include/amt_synth.h): the Fortran argument order

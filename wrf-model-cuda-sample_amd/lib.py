@@ -179,6 +179,14 @@ SYMBOLS = {
     "amt_ensemble_cyclic_fill": (_I, [_P, _I]),
     "amt_ensemble_set_cyclic": (_I, [_P, _I]),
     "amt_ensemble_cyclic": (_I, [_P]),
+    "amt_spec_bdy_update_device_f32": (_I, [_P, _I] + [_P] * 5 + [ctypes.c_float] + [_I] * (3 + 17)),
+    "amt_spec_bdy_update_device_f64": (_I, [_P, _I] + [_P] * 5 + [ctypes.c_double] + [_I] * (3 + 17)),
+    "amt_domain_spec_bdy_update": (_I, [_P]),
+    "amt_domain_set_spec_bdy": (_I, [_P, _I]),
+    "amt_domain_spec_bdy": (_I, [_P]),
+    "amt_ensemble_spec_bdy_update": (_I, [_P]),
+    "amt_ensemble_set_spec_bdy": (_I, [_P, _I]),
+    "amt_ensemble_spec_bdy": (_I, [_P]),
     "amt_stats_device_f32": (_I, [_P, _P, _I, _I] + [_I] * 12 + [ctypes.POINTER(FieldStats)]),
     "amt_stats_device_f64": (_I, [_P, _P, _I, _I] + [_I] * 12 + [ctypes.POINTER(FieldStats)]),
     "amt_compare_device_f32": (_I, [_P, _P, _P, _I, _I] + [_I] * 12 + [ctypes.POINTER(FieldDiff)]),

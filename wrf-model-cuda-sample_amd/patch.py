@@ -407,13 +407,15 @@ class NativeSlabStepper:
     ``transport``: "rccl" (ncclSend/ncclRecv), or "ipc" (peer copies between the processes of one node through
     hipIpcMemHandles and a shared-memory mailbox: no RCCL, ranks may share one device).
     Creating it is collective over the ``world`` ranks (ncclCommInitRank / the IPC set-up).
+    ``spec_bdy``: every sweep is followed by the boundary-zone update of this rank's own tile (``amt_domain_set_spec_bdy``,
+    header section 12; specified / nested domains).
     """
 
     NO_OVERLAP, LOOPBACK, TRANSPORT_IPC = 1, 2, 4          # enum amt_slab_flags
 
     def __init__(self, patch: Patch, rank: int, world: int, unique_id: Optional[bytes] = None, *,
                  stream=None, overlap: bool = True, variant: int = 0, loopback: bool = False, transport: str = "rccl",
-                 cyclic=(False, False)):
+                 cyclic=(False, False), spec_bdy: bool = False):
         import ctypes
         import torch
         from . import lib as _lib
@@ -443,6 +445,8 @@ class NativeSlabStepper:
             try:
                 _lib.check(L.amt_domain_set_scalars(self._dom, patch.rdx, patch.rdy, patch.dts, patch.epssm))
                 _lib.check(L.amt_domain_set_variant(self._dom, int(variant)))
+                if spec_bdy:                                  # the boundary-zone update behind every sweep (header section 12)
+                    _lib.check(L.amt_domain_set_spec_bdy(self._dom, 1))
                 if transport not in ("rccl", "ipc"):
                     raise ValueError("transport is 'rccl' or 'ipc'")
                 flags = ((0 if overlap else self.NO_OVERLAP) | (self.LOOPBACK if loopback else 0)
@@ -537,7 +541,7 @@ class NativeGridStepper:
 
     def __init__(self, patch: Patch, ri: int, rj: int, pi: int, pj: int, unique_id: Optional[bytes] = None, *,
                  stream=None, overlap: bool = True, variant: int = 0, loopback: bool = False, transport: str = "rccl",
-                 cyclic=(False, False)):
+                 cyclic=(False, False), spec_bdy: bool = False):
         import ctypes
         import torch
         from . import lib as _lib
@@ -567,6 +571,8 @@ class NativeGridStepper:
             try:
                 _lib.check(L.amt_domain_set_scalars(self._dom, patch.rdx, patch.rdy, patch.dts, patch.epssm))
                 _lib.check(L.amt_domain_set_variant(self._dom, int(variant)))
+                if spec_bdy:                                  # the boundary-zone update behind every sweep (header section 12)
+                    _lib.check(L.amt_domain_set_spec_bdy(self._dom, 1))
                 flags = ((0 if overlap else self.NO_OVERLAP) | (self.LOOPBACK if loopback else 0)
                          | (self.TRANSPORT_IPC if transport == "ipc" else 0)
                          | (CYCLIC_X_FLAG if self.cyclic[0] else 0) | (CYCLIC_Y_FLAG if self.cyclic[1] else 0))
@@ -698,12 +704,13 @@ class ExternalGridStepper:
     ``begin()`` (pack + interior), ``halo_wait()``, the host copies every ``send`` into the matching ``recv`` of the peer (an
     MPI host: Isend / Irecv with tag = side), ``end()`` (unpack + boundary cells).  Creation is not collective and needs no
     communicator id; any number of steppers may share a process and a device.  ``host_buffers``: the messages lie in
-    page-locked host memory (an MPI that is not GPU-aware)."""
+    page-locked host memory (an MPI that is not GPU-aware).  ``spec_bdy``: ``end()`` is followed by the boundary-zone update of
+    this rank's own tile (``amt_domain_set_spec_bdy``; nothing is exchanged for it)."""
 
     _HANDLE, _SLAB = "amt_grid", False
 
     def __init__(self, patch: Patch, ri: int, rj: int, pi: int, pj: int, *, cyclic=(False, False), overlap: bool = True,
-                 host_buffers: bool = False, stream=None, variant: int = 0):
+                 host_buffers: bool = False, stream=None, variant: int = 0, spec_bdy: bool = False):
         import ctypes
         import torch
         from . import lib as _lib
@@ -734,6 +741,8 @@ class ExternalGridStepper:
             try:
                 _lib.check(L.amt_domain_set_scalars(self._dom, patch.rdx, patch.rdy, patch.dts, patch.epssm))
                 _lib.check(L.amt_domain_set_variant(self._dom, int(variant)))
+                if spec_bdy:                                  # the boundary-zone update behind every sweep (header section 12)
+                    _lib.check(L.amt_domain_set_spec_bdy(self._dom, 1))
                 self.flags = (EXTERNAL_FLAG | (0 if overlap else 1) | (HOST_BUFFERS_FLAG if host_buffers else 0)
                               | (CYCLIC_X_FLAG if self.cyclic[0] else 0) | (CYCLIC_Y_FLAG if self.cyclic[1] else 0))
                 if self._SLAB:

@@ -230,6 +230,18 @@ class NativeDomain(_lib.HandleDiag):
         """``amt_domain_cyclic_fill``: one refresh now, asynchronous on the handle's stream."""
         _lib.check(self.L.amt_domain_cyclic_fill(self.handle, int(axes)))
 
+    def set_spec_bdy(self, on: bool = True) -> None:
+        """``amt_domain_set_spec_bdy``: every sweep of the handle's stepping is then followed by the boundary-zone update of a
+        specified / nested domain (header section 12).  False = off."""
+        _lib.check(self.L.amt_domain_set_spec_bdy(self.handle, int(bool(on))))
+
+    def spec_bdy(self) -> bool:
+        return bool(self.L.amt_domain_spec_bdy(self.handle))
+
+    def spec_bdy_update(self) -> None:
+        """``amt_domain_spec_bdy_update``: one update now, asynchronous on the handle's stream."""
+        _lib.check(self.L.amt_domain_spec_bdy_update(self.handle))
+
     def view(self, field_id: int, shape, typestr: str):
         ptr = self.L.amt_domain_field_ptr(self.handle, field_id)
         if not ptr:
