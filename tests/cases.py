@@ -42,6 +42,14 @@ def digest(a) -> str:
     return hashlib.sha256(np.ascontiguousarray(a).view(np.uint8).tobytes()).hexdigest()
 
 
+def digest_canonical_nan(a) -> str:
+    """digest() after mapping every NaN to the positive quiet NaN without payload: which NaN a platform generates or propagates
+    is not part of the comparison (tests/special_values.py)."""
+    a = np.ascontiguousarray(a).copy()
+    a[np.isnan(a)] = np.nan
+    return digest(a)
+
+
 def make_case(pkg, shape_name, flag_name, dtype, seed=12345, aligned=False):
     ni, nk, nj, tile = SHAPES[shape_name]
     b = pkg.synth.domain_bounds(ni, nk, nj, aligned=aligned)

@@ -18,6 +18,9 @@ lie into oracle/_ref/ (oracle/Makefile `ref`; nothing is copied into the reposit
 * hard_inputs_digests.json -- sha256 of the 7 outputs (and of the 4 vertical metrics going in) of every
                           shape of cases.SHAPES plus a tall sub-tile, every flag combination, fp32 and fp64,
                           with the WRF-like metrics and each scalar set of tests/hard_inputs.py
+* special_values_digests.json -- sha256, every NaN mapped to one bit pattern (cases.digest_canonical_nan), of the 7 outputs of
+                          the regimes of tests/special_values.py on three small shapes, every flag combination, fp32 and
+                          fp64; of every single plant on 37x5x11_ragged one digest over the 7 outputs
 
 The reference ships no golden vectors of its own (its drivers diff against an absent
 /data2/... directory), so these are the pinned known answers.
@@ -36,6 +39,7 @@ sys.path.insert(0, str(ROOT / "tests"))
 import __graft_entry__ as g  # noqa: E402
 import cases  # noqa: E402
 import hard_inputs  # noqa: E402
+import special_values  # noqa: E402
 
 
 FULL_SHAPES = ("37x5x11_ragged", "130x3x7_tile", "70x1x9_onelevel")   # stored as full arrays
@@ -64,6 +68,7 @@ def main():
     print(f"wrote {len(small)} arrays, {len(digests)} cases")
     extra_reference_digests(pkg, oracle)
     hard_inputs_digests(pkg, oracle)
+    special_values_digests(pkg, oracle)
 
 
 def extra_reference_digests(pkg, oracle):
@@ -93,5 +98,26 @@ def hard_inputs_digests(pkg, oracle):
     print(f"wrote {len(recs)} hard-input cases")
 
 
+def special_values_digests(pkg, oracle):
+    recs = {}
+    for key in special_values.regime_keys():
+        p = special_values.special_case(pkg, key)
+        oracle.ref_advance_mu_t(*p.args())
+        recs[key] = {"bounds": list(p.bounds.as_tuple()), "scalars": [p.rdx, p.rdy, p.dts, p.epssm], "seed": special_values.SEED,
+                     "outputs": {n: cases.digest_canonical_nan(p.arrays[n]) for n in pkg.synth.OUTPUTS}}
+    for key in special_values.plant_keys():
+        p = special_values.special_case(pkg, key)
+        oracle.ref_advance_mu_t(*p.args())
+        canon = [special_values.canonical_nan(p.arrays[n]).view(np.uint8).ravel() for n in pkg.synth.OUTPUTS]
+        recs[key] = {"outputs": cases.digest(np.concatenate(canon))}
+    (HERE / "special_values_digests.json").write_text(json.dumps(recs, indent=0, sort_keys=True))
+    print(f"wrote {len(recs)} special-value cases")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["special_values"]:                   # this file alone; the others stay as they are
+        _oracle = g.load_oracle()
+        _oracle.build(ref=True)
+        special_values_digests(g.load_package(), _oracle)
+    else:
+        main()
