@@ -8,6 +8,10 @@ MODULE amt_c_binding
 
    integer(c_int), parameter :: AMT_OK = 0
    integer(c_int), parameter :: AMT_ERR_NONFINITE = 7         ! the non-finite guard of header section 10 has a finding
+   ! enum amt_variant (amt_*_set_variant, the `variant` argument of amt_advance_mu_t_device_* and its ensemble twin);
+   ! AMT_LAUNCH_BESIDE_OTHERS is OR-ed into that argument
+   integer(c_int), parameter :: AMT_VARIANT_AUTO = 0, AMT_VARIANT_COLUMN = 1, AMT_VARIANT_MARCH = 2
+   integer(c_int), parameter :: AMT_LAUNCH_BESIDE_OTHERS = 256
    ! enum amt_region (amt_domain_field_stats, amt_domain_compare and their ensemble twins)
    integer(c_int), parameter :: AMT_REGION_WINDOW = 0, AMT_REGION_MEMORY = 1
 
@@ -149,9 +153,70 @@ MODULE amt_c_binding
          import :: c_ptr
          type(c_ptr) :: msg
       end function
+      ! NUL-terminated C strings owned by the library: the build's version line, the text of an amt_status code
+      function amt_version() bind(C, name="amt_version") result(msg)
+         import :: c_ptr
+         type(c_ptr) :: msg
+      end function
+      function amt_status_string(status) bind(C, name="amt_status_string") result(msg)
+         import :: c_ptr, c_int
+         integer(c_int), value :: status
+         type(c_ptr) :: msg
+      end function
       function amt_device_count() bind(C, name="amt_device_count") result(n)
          import :: c_int
          integer(c_int) :: n
+      end function
+
+      ! (2) device-resident drop-ins: every array argument is a DEVICE address, the call is enqueued on hip_stream and returns
+      ! without synchronising; variant = AMT_VARIANT_* below
+      function amt_advance_mu_t_device_f32(hip_stream, variant,                                  &
+                                    ww, ww_1, u, u_1, v, v_1, mu, mut, muave, muts, muu, muv,    &
+                                    mudf, t, t_1, t_ave, ft, mu_tend, rdx, rdy, dts, epssm,      &
+                                    dnw, fnm, fnp, rdnw, msfuy, msfvx_inv, msftx, msfty,         &
+                                    periodic_x, specified, nested,                               &
+                                    ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,       &
+                                    its, ite, jts, jte, kts, kte)                                &
+            bind(C, name="amt_advance_mu_t_device_f32") result(rc)
+         import :: c_ptr, c_float, c_int
+         type(c_ptr), value :: hip_stream                    ! hipStream_t, c_null_ptr = the default stream
+         integer(c_int), value :: variant
+         type(c_ptr), value :: ww, ww_1, u, u_1, v, v_1, mu, mut, muave, muts, muu, muv      ! DEVICE addresses
+         type(c_ptr), value :: mudf, t, t_1, t_ave, ft, mu_tend
+         real(c_float), value :: rdx, rdy, dts, epssm
+         type(c_ptr), value :: dnw, fnm, fnp, rdnw, msfuy, msfvx_inv, msftx, msfty
+         integer(c_int), value :: periodic_x, specified, nested
+         integer(c_int), value :: ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme
+         integer(c_int), value :: its, ite, jts, jte, kts, kte
+         integer(c_int) :: rc
+      end function
+      function amt_advance_mu_t_device_f64(hip_stream, variant,                                  &
+                                    ww, ww_1, u, u_1, v, v_1, mu, mut, muave, muts, muu, muv,    &
+                                    mudf, t, t_1, t_ave, ft, mu_tend, rdx, rdy, dts, epssm,      &
+                                    dnw, fnm, fnp, rdnw, msfuy, msfvx_inv, msftx, msfty,         &
+                                    periodic_x, specified, nested,                               &
+                                    ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,       &
+                                    its, ite, jts, jte, kts, kte)                                &
+            bind(C, name="amt_advance_mu_t_device_f64") result(rc)
+         import :: c_ptr, c_double, c_int
+         type(c_ptr), value :: hip_stream                    ! hipStream_t, c_null_ptr = the default stream
+         integer(c_int), value :: variant
+         type(c_ptr), value :: ww, ww_1, u, u_1, v, v_1, mu, mut, muave, muts, muu, muv      ! DEVICE addresses
+         type(c_ptr), value :: mudf, t, t_1, t_ave, ft, mu_tend
+         real(c_double), value :: rdx, rdy, dts, epssm
+         type(c_ptr), value :: dnw, fnm, fnp, rdnw, msfuy, msfvx_inv, msftx, msfty
+         integer(c_int), value :: periodic_x, specified, nested
+         integer(c_int), value :: ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme
+         integer(c_int), value :: its, ite, jts, jte, kts, kte
+         integer(c_int) :: rc
+      end function
+      ! the compute window the routine updates for these flags and bounds (host arithmetic, no device)
+      function amt_compute_window(periodic_x, specified, nested, ids, ide, jds, jde, its, ite, jts, jte, kts, kte,      &
+                                  i_start, i_end, j_start, j_end, k_start, k_end) bind(C, name="amt_compute_window") result(rc)
+         import :: c_int
+         integer(c_int), value :: periodic_x, specified, nested, ids, ide, jds, jde, its, ite, jts, jte, kts, kte
+         integer(c_int) :: i_start, i_end, j_start, j_end, k_start, k_end
+         integer(c_int) :: rc
       end function
 
       ! (3) resident domain handle
@@ -164,6 +229,36 @@ MODULE amt_c_binding
          integer(c_int), value :: ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme
          integer(c_int), value :: its, ite, jts, jte, kts, kte
          integer(c_int) :: rc
+      end function
+      ! over device arrays the caller owns: fields(0:25) = the device addresses in amt_field order; nothing is copied or freed
+      function amt_domain_wrap(handle, dtype_bytes, periodic_x, specified, nested,               &
+                               ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,            &
+                               its, ite, jts, jte, kts, kte, fields, hip_stream) bind(C, name="amt_domain_wrap") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr) :: handle                      ! amt_domain **
+         integer(c_int), value :: dtype_bytes, periodic_x, specified, nested
+         integer(c_int), value :: ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme
+         integer(c_int), value :: its, ite, jts, jte, kts, kte
+         type(c_ptr), intent(in) :: fields(*)
+         type(c_ptr), value :: hip_stream           ! c_null_ptr: a stream of the handle's own
+         integer(c_int) :: rc
+      end function
+      function amt_domain_set_variant(handle, variant) bind(C, name="amt_domain_set_variant") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: variant
+         integer(c_int) :: rc
+      end function
+      function amt_domain_field_ptr(handle, field) bind(C, name="amt_domain_field_ptr") result(ptr)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: field
+         type(c_ptr) :: ptr                         ! device address, c_null_ptr on error
+      end function
+      function amt_domain_stream(handle) bind(C, name="amt_domain_stream") result(stream)
+         import :: c_ptr
+         type(c_ptr), value :: handle
+         type(c_ptr) :: stream                      ! hipStream_t
       end function
       function amt_domain_destroy(handle) bind(C, name="amt_domain_destroy") result(rc)
          import :: c_ptr, c_int
@@ -187,6 +282,27 @@ MODULE amt_c_binding
          type(c_ptr), value :: handle, host
          integer(c_int), value :: field
          integer(c_int) :: rc
+      end function
+      ! rows j_lo..j_hi (Fortran indices inside jms:jme) of a rank-3 or rank-2 field; host holds exactly those rows
+      function amt_domain_upload_rows(handle, field, j_lo, j_hi, host) bind(C, name="amt_domain_upload_rows") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle, host
+         integer(c_int), value :: field, j_lo, j_hi
+         integer(c_int) :: rc
+      end function
+      function amt_domain_download_rows(handle, field, j_lo, j_hi, host) bind(C, name="amt_domain_download_rows") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle, host
+         integer(c_int), value :: field, j_lo, j_hi
+         integer(c_int) :: rc
+      end function
+      ! allocations timed by the last placement sampling of this handle (0: none) and their sweep times
+      function amt_domain_placement(handle, ms_per_try, cap) bind(C, name="amt_domain_placement") result(n)
+         import :: c_ptr, c_int, c_float
+         type(c_ptr), value :: handle
+         real(c_float) :: ms_per_try(*)
+         integer(c_int), value :: cap
+         integer(c_int) :: n
       end function
       function amt_domain_step(handle, n_sweeps) bind(C, name="amt_domain_step") result(rc)
          import :: c_ptr, c_int
@@ -250,6 +366,17 @@ MODULE amt_c_binding
          integer(c_int), value :: device
          integer(c_int) :: rc
       end function
+      ! rank 0: a fresh communicator id (128 bytes) to hand to every rank, for hosts that broadcast it themselves (MPI_Bcast)
+      function amt_comm_unique_id(id_out) bind(C, name="amt_comm_unique_id") result(rc)
+         import :: c_char, c_int
+         character(kind=c_char), intent(out) :: id_out(128)
+         integer(c_int) :: rc
+      end function
+      ! a value all processes of one launch agree on and two launches do not (an unsigned 64-bit pattern)
+      function amt_comm_launch_nonce() bind(C, name="amt_comm_launch_nonce") result(nonce)
+         import :: c_int64_t
+         integer(c_int64_t) :: nonce
+      end function
       function amt_comm_rendezvous_file(path, nonce, rank, world, timeout_s, id_out)              &
             bind(C, name="amt_comm_rendezvous_file") result(rc)
          import :: c_char, c_int, c_double, c_int64_t
@@ -271,6 +398,17 @@ MODULE amt_c_binding
          import :: c_ptr, c_int
          type(c_ptr), value :: slab
          integer(c_int) :: rc
+      end function
+      function amt_slab_exchange(slab) bind(C, name="amt_slab_exchange") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: slab
+         integer(c_int) :: rc
+      end function
+      ! NUL-terminated C string: "rccl", "ipc", "external" or "none" (no neighbour)
+      function amt_slab_transport(slab) bind(C, name="amt_slab_transport") result(msg)
+         import :: c_ptr
+         type(c_ptr), value :: slab
+         type(c_ptr) :: msg
       end function
       function amt_slab_step(slab, n_sweeps) bind(C, name="amt_slab_step") result(rc)
          import :: c_ptr, c_int
@@ -330,6 +468,11 @@ MODULE amt_c_binding
          import :: c_ptr, c_int
          type(c_ptr), value :: grid
          integer(c_int) :: rc
+      end function
+      function amt_grid_transport(grid) bind(C, name="amt_grid_transport") result(msg)
+         import :: c_ptr
+         type(c_ptr), value :: grid
+         type(c_ptr) :: msg
       end function
       function amt_grid_step(grid, n_sweeps) bind(C, name="amt_grid_step") result(rc)
          import :: c_ptr, c_int
@@ -459,6 +602,25 @@ MODULE amt_c_binding
          integer(c_int64_t), value :: seed
          integer(c_long), value :: idim, kdim, jdim, gi0, gk0, gj0, gidim, gkdim, gjdim
          integer(c_int) :: rc
+      end function
+
+      ! the same generator on the device: dst_device is a DEVICE address, asynchronous on hip_stream; identical bits
+      function amt_synth_fill_device(hip_stream, field, dtype_bytes, dst_device, seed, idim, kdim, jdim, gi0, gk0, gj0, &
+                                     gidim, gkdim, gjdim) bind(C, name="amt_synth_fill_device") result(rc)
+         import :: c_ptr, c_int, c_long, c_int64_t
+         type(c_ptr), value :: hip_stream
+         integer(c_int), value :: field, dtype_bytes
+         type(c_ptr), value :: dst_device
+         integer(c_int64_t), value :: seed
+         integer(c_long), value :: idim, kdim, jdim, gi0, gk0, gj0, gidim, gkdim, gjdim
+         integer(c_int) :: rc
+      end function
+      ! rows per workgroup of a single patch's launch (host arithmetic; amt_march_rows_for_members with members = 1)
+      function amt_march_rows_for(ntile_i, nj, cus, max_rows, wbytes, hl) bind(C, name="amt_march_rows_for") result(rows)
+         import :: c_int, c_long
+         integer(c_long), value :: ntile_i, max_rows
+         integer(c_int), value :: nj, cus, wbytes, hl
+         integer(c_int) :: rows
       end function
 
       ! (8) ensembles: `members` patches of one shape, every 3-D and 2-D array with one more, slowest, dimension --
