@@ -863,6 +863,47 @@ int amt_ensemble_spec_bdy_update(amt_ensemble *e);
 int amt_ensemble_set_spec_bdy(amt_ensemble *e, int on);
 int amt_ensemble_spec_bdy(const amt_ensemble *e);
 
+/* ------------------------------------------------------------------------
+ * (13) Ensemble mean, variance and envelope of a member-stacked field, on the device: what an ensemble host asks at every
+ *      output time, without downloading `members` x the field.  INPUT: a BOX exactly as in (10) -- Fortran-inclusive i0..i1,
+ *      k0..k1, j0..j1 inside the extents ims:ime, kms:kme, jms:jme of a rank-3 or rank-2 field (rank 2 ignores k) -- of the
+ *      array `a`, member-stacked as in (8) with members = M >= 1: member m's base is a + m * idim*kdim*jdim (kdim = 1 for
+ *      rank 2).  OUTPUTS: mean, var, lo, hi, each an array of ONE member's extents and of a's type, each may be NULL ("not
+ *      wanted"), at least one must be given.  For every cell c of the box, in member order, with x_m = a_m[c]:
+ *        mean  s = double(x_0); for m = 1..M-1: s = s + double(x_m);  mean_d = s / double(M);  mean[c] = T(mean_d), rounded
+ *              to nearest even.  With M = 1 the mean is x_0 itself, -0.0 included.
+ *        var   q = 0.0; for m = 0..M-1: d = double(x_m) - mean_d; q = q + d*d;  var_d = q / double(max(M-1, 1));
+ *              var[c] = T(var_d): the unbiased sample variance; a single finite member gives +0.0.  d*d is a product, then a
+ *              sum (no fused multiply-add).  There is no square root here: the caller takes it.
+ *        lo    a NaN if any x_m is NaN (its payload is not part of the contract); otherwise the FIRST member, in member
+ *              order, that attains the minimum: lo = x_0; if (x_m < lo) lo = x_m -- so the sign of a zero is that member's.
+ *        hi    the same with >.
+ *      +-Inf follow IEEE through these expressions (+Inf and -Inf in one cell: a NaN mean).  Every cell outside the box, in
+ *      every output array, keeps its bits; no cell of `a` outside the box is read (halo cells may hold NaN), nothing outside
+ *      the arrays is read or written.  The order is per cell and sequential over the members: a result is a function of the
+ *      box contents alone -- not of addresses, alignment, stream, run or launch geometry (no atomics, no workspace).
+ *      AMT_ERR_INVALID_ARG, reported before any device call, with or without a device, the outputs untouched: a NULL `a`;
+ *      all four outputs NULL; members < 1; a rank that is not 2 or 3 (a rank-1 field at handle level); an unknown region;
+ *      a box that is empty or outside the extents; an output whose address range (one member's extents) overlaps a's
+ *      (members x that) or another output's.
+ * ------------------------------------------------------------------------ */
+/* pointer level, beside amt_stats_device_*: asynchronous on hip_stream (NULL = the default stream); writes DEVICE arrays,
+ * needs no workspace and allocates nothing */
+int amt_moments_device_f32(void *hip_stream, const float *a, int rank, int members,
+                           int ims, int ime, int jms, int jme, int kms, int kme,
+                           int i0, int i1, int k0, int k1, int j0, int j1,
+                           float *mean, float *var, float *lo, float *hi);
+int amt_moments_device_f64(void *hip_stream, const double *a, int rank, int members,
+                           int ims, int ime, int jms, int jme, int kms, int kme,
+                           int i0, int i1, int k0, int k1, int j0, int j1,
+                           double *mean, double *var, double *lo, double *hi);
+/* handle level: field `field` (rank 2 or 3, amt_field_rank) of the ensemble over AMT_REGION_WINDOW or AMT_REGION_MEMORY, with
+ * the meaning amt_ensemble_field_stats gives them.  Asynchronous on the ensemble's stream (wrapped handles: the caller's),
+ * behind whatever is enqueued there; amt_ensemble_sync waits for it.  The outputs are caller-owned device arrays of one
+ * member's extents and the handle's type -- for instance amt_domain_field_ptr of an amt_domain of the same shape, which
+ * amt_domain_field_stats, amt_domain_compare and amt_domain_download then understand. */
+int amt_ensemble_moments(amt_ensemble *e, int field, int region, void *mean, void *var, void *lo, void *hi);
+
 #ifdef __cplusplus
 }
 #endif

@@ -321,11 +321,11 @@ struct DiagExtents { int ims, ime, jms, jme, kms, kme; };
 struct DiagBoxArg { int i0, i1, k0, k1, j0, j1; };
 
 // Argument checks and the launch plan: host arithmetic only.
-int diag_plan(const char *who, int rank, int members, const DiagExtents &x, DiagBoxArg bxa, AmtDiagBox &box)
+int diag_plan(const char *who, int rank, int members, const DiagExtents &x, DiagBoxArg bxa, AmtDiagBox &box, int max_members = 65535)
 {
     if (rank != 2 && rank != 3) return amt_fail(AMT_ERR_INVALID_ARG, "%s: rank = %d: only rank-2 and rank-3 fields have a box", who, rank);
     if (members < 1) return amt_fail(AMT_ERR_INVALID_ARG, "%s: members = %d: an ensemble has at least one member", who, members);
-    if (members > 65535) return amt_fail(AMT_ERR_INVALID_ARG, "%s: %d members: one launch covers at most 65535", who, members);
+    if (members > max_members) return amt_fail(AMT_ERR_INVALID_ARG, "%s: %d members: one launch covers at most %d", who, members, max_members);
     if (x.ime < x.ims || x.jme < x.jms || (rank == 3 && x.kme < x.kms)) return amt_fail(AMT_ERR_INVALID_ARG, "%s: empty memory extents", who);
     if (rank == 2) { bxa.k0 = bxa.k1 = 0; }
     if (bxa.i1 < bxa.i0 || bxa.j1 < bxa.j0 || bxa.k1 < bxa.k0)
@@ -493,7 +493,7 @@ int diag_device_call(const char *who, void *hip_stream, int dtype_bytes, bool cm
 }
 
 // the box of a region of a field of a handle; AMT_OK with *empty set when the compute window holds no cell
-int diag_region(const char *who, const amt_domain *d, int field, int region, int members, AmtDiagBox &box, bool *empty)
+int diag_region(const char *who, const amt_domain *d, int field, int region, int members, AmtDiagBox &box, bool *empty, int max_members = 65535)
 {
     *empty = false;
     if (field < 0 || field >= AMT_F_COUNT) return amt_fail(AMT_ERR_INVALID_ARG, "%s: unknown field %d", who, field);
@@ -510,7 +510,7 @@ int diag_region(const char *who, const amt_domain *d, int field, int region, int
     } else {
         return amt_fail(AMT_ERR_INVALID_ARG, "%s: region = %d is neither AMT_REGION_WINDOW nor AMT_REGION_MEMORY", who, region);
     }
-    return diag_plan(who, rank, members, DiagExtents{d->ims, d->ime, d->jms, d->jme, d->kms, d->kme}, b, box);
+    return diag_plan(who, rank, members, DiagExtents{d->ims, d->ime, d->jms, d->jme, d->kms, d->kme}, b, box, max_members);
 }
 
 int diag_state(const char *who, amt_domain *d)
@@ -666,6 +666,27 @@ void amt_diag_release(amt_domain *d)
     delete d->diag;
     d->diag = nullptr;
     d->guard_every = 0;
+}
+
+// the same checks for the passes that keep no member axis in their grid (amt_moments.hip): any member count
+static void diag_box_out(const AmtDiagBox &b, AmtBox *box)
+{
+    *box = AmtBox{b.idim, b.jstride, b.mstride, b.first, b.ni, b.nk, b.nj};
+}
+int amt_box_plan(const char *who, int rank, int members, int ims, int ime, int jms, int jme, int kms, int kme,
+                 int i0, int i1, int k0, int k1, int j0, int j1, AmtBox *box)
+{
+    AmtDiagBox b{};
+    const int rc = diag_plan(who, rank, members, DiagExtents{ims, ime, jms, jme, kms, kme}, DiagBoxArg{i0, i1, k0, k1, j0, j1}, b, INT_MAX);
+    if (rc == AMT_OK) diag_box_out(b, box);
+    return rc;
+}
+int amt_box_region(const char *who, const amt_domain *d, int field, int region, int members, AmtBox *box, bool *empty)
+{
+    AmtDiagBox b{};
+    const int rc = diag_region(who, d, field, region, members, b, empty, INT_MAX);
+    if (rc == AMT_OK && !*empty) diag_box_out(b, box);
+    return rc;
 }
 
 #define AMT_DIAG_BOX_SIG int ims, int ime, int jms, int jme, int kms, int kme, int i0, int i1, int k0, int k1, int j0, int j1

@@ -244,3 +244,21 @@ int amt_bdy_check_domain(const char *who, const amt_domain *d, int members);
 int amt_diag_guard_status(const char *who, const amt_domain *d);
 int amt_diag_after_sweep(const char *who, amt_domain *d, int members);
 void amt_diag_release(amt_domain *d);
+
+// ---------------------------------------------------------------------------
+// The BOX of header section 10, for the other passes over resident state (amt_moments.hip): the checks of amt_diag.hip and
+// what they work out, in elements -- host arithmetic only, an error is AMT_ERR_INVALID_ARG with its text.
+//   amt_box_plan:   a box i0..i1, k0..k1, j0..j1 inside the extents of a rank-2 / rank-3 field (rank 2 ignores k)
+//   amt_box_region: AMT_REGION_WINDOW / AMT_REGION_MEMORY of a field of a handle; *empty (with AMT_OK) when the compute
+//                   window holds no cell
+// ---------------------------------------------------------------------------
+struct AmtBox {
+    long idim;        // elements of a memory row of i
+    long jstride;     // elements from row j to row j + 1
+    long mstride;     // elements from member m to member m + 1
+    long first;       // offset of the box's first element from the member's base
+    int ni, nk, nj;   // the box; nk = 1 for rank 2
+};
+int amt_box_plan(const char *who, int rank, int members, int ims, int ime, int jms, int jme, int kms, int kme,
+                 int i0, int i1, int k0, int k1, int j0, int j1, AmtBox *box);
+int amt_box_region(const char *who, const amt_domain *d, int field, int region, int members, AmtBox *box, bool *empty);

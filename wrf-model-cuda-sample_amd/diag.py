@@ -10,6 +10,10 @@ for it.
 shape); ``box = (i0, i1, k0, k1, j0, j1)`` is Fortran-inclusive inside them (default: everything; rank 2 ignores the k
 entries).  Offsets in the records count elements from the member's base.  Argument errors raise ``AmtError`` with status
 ERR_INVALID_ARG before any device call.
+
+``moments(a)`` takes a member-STACKED tensor -- ``(members, jdim, kdim, idim)`` or ``(members, jdim, idim)`` -- and returns the
+ensemble mean, sample variance and envelope over the members as device tensors of one member's shape (header section 13,
+``amt_moments_device_*``): one streaming pass, asynchronous on ``stream``.
 """
 from __future__ import annotations
 
@@ -81,3 +85,50 @@ def compare(a, b, *, stacked: bool = False, extents=None, box=None, stream=None)
         _lib.check(fn(ctypes.c_void_p(_stream_handle(a, stream)), ctypes.c_void_p(a.data_ptr()), ctypes.c_void_p(b.data_ptr()),
                       rank, members, *ext, *bx, out))
     return list(out)
+
+
+MOMENTS = ("mean", "var", "lo", "hi")
+
+
+def moments_outputs(names, out, shape, dtype, device, alloc_stream_is_call_stream: bool):
+    """The four output slots of a moments call: ``(tensors by name, [pointer or None] * 4)``.  A name of ``names`` without a
+    tensor in ``out`` gets a zero-filled one (``+0.0`` outside the box); a tensor passed in keeps its cells outside the box."""
+    import torch
+    out = dict(out or {})
+    names = tuple(names) + tuple(k for k in out if k not in names)
+    for k in names:
+        if k not in MOMENTS:
+            raise _lib.AmtError(_lib.ERR_INVALID_ARG, f"unknown moment {k!r}: one of {MOMENTS}")
+    res, fresh = {}, False
+    for k in MOMENTS:
+        if k not in names:
+            continue
+        t = out.get(k)
+        if t is None:
+            t = torch.zeros(shape, dtype=dtype, device=device)
+            fresh = True
+        elif not (_is_torch(t) and t.is_cuda and t.is_contiguous() and t.dtype == dtype and tuple(t.shape) == tuple(shape)
+                  and t.device == device):
+            raise _lib.AmtError(_lib.ERR_INVALID_ARG, f"out[{k!r}]: need a contiguous {dtype} device tensor of shape {tuple(shape)} "
+                                                      "on the input's device")
+        res[k] = t
+    if fresh and not alloc_stream_is_call_stream:
+        torch.cuda.current_stream(device).synchronize()       # the zeros are there before another stream writes the box
+    return res, [ctypes.c_void_p(res[k].data_ptr()) if k in res else None for k in MOMENTS]
+
+
+def moments(a, *, extents=None, box=None, stream=None, want=("mean", "var"), out=None):
+    """Mean, sample variance, minimum and maximum over the members of the box of the stacked tensor ``a``, cell by cell in member
+    order (the definition: header section 13).  Returns a dict name -> tensor for every name of ``want`` and every key of
+    ``out``.  A tensor the call allocates is ``+0.0`` outside the box; one passed in through ``out={"mean": t, ...}`` keeps its
+    cells outside the box.  Asynchronous on ``stream`` (default: torch's current stream)."""
+    L = _lib.load_library()
+    rank, members, ext, bx, sfx = _plan(a, True, extents, box)
+    import torch
+    call_stream = _stream_handle(a, stream)
+    same = call_stream == torch.cuda.current_stream(a.device).cuda_stream
+    res, ptrs = moments_outputs(want, out, tuple(a.shape[1:]), a.dtype, a.device, same)
+    fn = getattr(L, f"amt_moments_device_{sfx}")
+    with torch.cuda.device(a.device):
+        _lib.check(fn(ctypes.c_void_p(call_stream), ctypes.c_void_p(a.data_ptr()), rank, members, *ext, *bx, *ptrs))
+    return res

@@ -210,6 +210,23 @@ class Ensemble(_lib.HandleDiag):
         """``amt_ensemble_spec_bdy_update``: one update of every member now, asynchronous on the handle's stream."""
         _lib.check(self.L.amt_ensemble_spec_bdy_update(self.handle))
 
+    def moments(self, field, region="window", want=("mean", "var"), out=None) -> dict:
+        """``amt_ensemble_moments``: mean, sample variance, minimum and maximum over the members of ``field`` (a name or an
+        ``amt_field`` id, rank 2 or 3) over ``region`` ("window" / "memory" or REGION_*), as torch tensors of ONE member's shape
+        on the current device.  Returns a dict name -> tensor for every name of ``want`` and every key of ``out``; a tensor the
+        call allocates is ``+0.0`` outside the region, one passed in through ``out`` keeps its cells there.  Enqueued on the
+        handle's stream behind its stepping; ``sync()`` waits for it."""
+        import torch
+        from . import diag as _diag
+        name = field if isinstance(field, str) else _S.FIELD_NAMES[int(field)]
+        region = {"window": _lib.REGION_WINDOW, "memory": _lib.REGION_MEMORY}.get(region, region)
+        dt = torch.float64 if self.dtype == np.float64 else torch.float32
+        dev = torch.device("cuda", torch.cuda.current_device())
+        same = self.stream == torch.cuda.current_stream(dev).cuda_stream
+        res, ptrs = _diag.moments_outputs(want, out, tuple(self.bounds.shape(name)), dt, dev, same)
+        _lib.check(self.L.amt_ensemble_moments(self.handle, _S.FIELD_ID[name], int(region), *ptrs))
+        return res
+
     def sync(self) -> None:
         self._check(self.L.amt_ensemble_sync(self.handle))
 

@@ -9,11 +9,14 @@
 ! domain handle (device arrays kept across calls -- the kernel-only time the
 ! reference reports) and checks that both paths agree bit for bit.
 !
-!   advance_mu_t_driver [NI NK NJ [nsweeps [outdir [flags [placements]]]]]
+!   advance_mu_t_driver [NI NK NJ [nsweeps [outdir [flags [placements [members]]]]]]
 !     flags: 0 none, 1 specified, 2 nested, 3 specified+periodic_x
 !     placements: > 1 samples that many allocations of the resident state and keeps the fastest (amt_domain_tune_placement)
+!     members: > 0 adds an ensemble of that many members of the same shape (amt_ensemble_fill_synthetic, seeds seed + m),
+!              stepped nsweeps times, and its mean / variance / envelope over the members (header section 13)
 !   With outdir the 7 updated arrays are written there as raw native-endian
-!   streams <name>.bin for an external checker.
+!   streams <name>.bin for an external checker; with members the moments as ens_<field>_<mean|var|lo|hi>.bin:
+!   ww over the whole memory, mu over the compute window, t over the memory less one cell on every side (zero outside).
 program advance_mu_t_driver
   use iso_c_binding
   use amt_c_binding
@@ -39,7 +42,7 @@ program advance_mu_t_driver
   real(c_float) :: ms
   integer(kind=8) :: c0, c1, cmid, hz
   real(kind=8) :: cells, secs
-  integer :: nbad, ndef, ntune
+  integer :: nbad, ndef, ntune, members
   integer(c_int) :: nslots, slot_ids(16)
   real(c_float) :: tune_ms(8)
 
@@ -60,6 +63,10 @@ program advance_mu_t_driver
   if (command_argument_count() >= 7) then
      call get_command_argument(7, arg); read (arg, *) ntune
      ntune = min(ntune, 8)
+  end if
+  members = 0
+  if (command_argument_count() >= 8) then
+     call get_command_argument(8, arg); read (arg, *) members
   end if
   config_flags%specified  = (iflag == 1 .or. iflag == 3)
   config_flags%nested     = (iflag == 2)
@@ -263,7 +270,77 @@ program advance_mu_t_driver
   if (nbad /= 0) error stop 2
   if (ndef /= 0) error stop 5
 
+  if (members > 0) call ensemble_moments()
+
 contains
+
+  ! An ensemble of `members` members of this shape, stepped nsweeps times, and what a host asks of it at an output time: the
+  ! mean, the sample variance and the envelope over the members, computed where the members live.  The outputs are arrays of
+  ! ONE member's extents: those of a second amt_domain of the same shape serve, and come down with amt_domain_download.
+  subroutine ensemble_moments()
+    type(c_ptr) :: ens, outs, stream
+    real(wp), allocatable, target :: o3(:,:,:), o2(:,:)
+    integer(c_int) :: wb, px, sp, ne, fw(4), ft4(4), fm(4)
+    character(len=4), parameter :: mname(4) = ['mean', 'var ', 'lo  ', 'hi  ']
+    integer :: k
+    wb = int(storage_size(rdx)/8, c_int)
+    px = merge(1_c_int, 0_c_int, config_flags%periodic_x)
+    sp = merge(1_c_int, 0_c_int, config_flags%specified)
+    ne = merge(1_c_int, 0_c_int, config_flags%nested)
+    fw = [AMT_F_WW, AMT_F_WW_1, AMT_F_U, AMT_F_U_1]          ! the output arrays: four rank-3 fields each for ww and t,
+    ft4 = [AMT_F_T, AMT_F_T_1, AMT_F_T_AVE, AMT_F_FT]        ! four rank-2 fields for mu
+    fm = [AMT_F_MU, AMT_F_MUT, AMT_F_MUAVE, AMT_F_MUTS]
+    allocate (o3(ims:ime,kms:kme,jms:jme), o2(ims:ime,jms:jme))
+    call amt_check(amt_ensemble_create(ens, int(members, c_int), wb, px, sp, ne, ids, ide, jds, jde, kde,                  &
+                                       ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte), 'amt_ensemble_create')
+    call amt_check(amt_ensemble_set_scalars(ens, real(rdx, c_double), real(rdy, c_double), real(dts, c_double),          &
+                                            real(epssm, c_double)), 'amt_ensemble_set_scalars')
+    call amt_check(amt_ensemble_fill_synthetic(ens, seed, int(ims, c_long), int(kms-1, c_long), int(jms, c_long),        &
+                   int(ni+2, c_long), int(nk+1, c_long), int(nj+2, c_long)), 'amt_ensemble_fill_synthetic')
+    call amt_check(amt_ensemble_step(ens, int(nsweeps, c_int)), 'amt_ensemble_step')
+    call amt_check(amt_domain_create(outs, wb, px, sp, ne, ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,         &
+                                     its, ite, jts, jte, kts, kte), 'amt_domain_create')
+    o3 = 0.0_wp; o2 = 0.0_wp                                  ! what a cell outside the box keeps
+    do k = 1, 4
+       call amt_check(amt_domain_upload(outs, fw(k), c_loc(o3)), 'amt_domain_upload')
+       call amt_check(amt_domain_upload(outs, ft4(k), c_loc(o3)), 'amt_domain_upload')
+       call amt_check(amt_domain_upload(outs, fm(k), c_loc(o2)), 'amt_domain_upload')
+    end do
+    ! handle level, on the ensemble's stream behind the sweeps: no wait in between
+    call amt_check(amt_ensemble_moments(ens, AMT_F_WW, AMT_REGION_MEMORY, amt_domain_field_ptr(outs, fw(1)),             &
+                   amt_domain_field_ptr(outs, fw(2)), amt_domain_field_ptr(outs, fw(3)), amt_domain_field_ptr(outs, fw(4))), &
+                   'amt_ensemble_moments (ww)')
+    call amt_check(amt_ensemble_moments(ens, AMT_F_MU, AMT_REGION_WINDOW, amt_domain_field_ptr(outs, fm(1)),             &
+                   amt_domain_field_ptr(outs, fm(2)), amt_domain_field_ptr(outs, fm(3)), amt_domain_field_ptr(outs, fm(4))), &
+                   'amt_ensemble_moments (mu)')
+    ! pointer level, for a host that keeps its own stacked arrays: a box one cell inside the memory, on the same stream
+    stream = amt_ensemble_stream(ens)
+    if (wb == 8) then
+       rc = amt_moments_device_f64(stream, amt_ensemble_field_ptr(ens, AMT_F_T), 3_c_int, int(members, c_int),           &
+                                   ims, ime, jms, jme, kms, kme, ims + 1, ime - 1, kms + 1, kme - 1, jms + 1, jme - 1,   &
+                                   amt_domain_field_ptr(outs, ft4(1)), amt_domain_field_ptr(outs, ft4(2)),                &
+                                   amt_domain_field_ptr(outs, ft4(3)), amt_domain_field_ptr(outs, ft4(4)))
+    else
+       rc = amt_moments_device_f32(stream, amt_ensemble_field_ptr(ens, AMT_F_T), 3_c_int, int(members, c_int),           &
+                                   ims, ime, jms, jme, kms, kme, ims + 1, ime - 1, kms + 1, kme - 1, jms + 1, jme - 1,   &
+                                   amt_domain_field_ptr(outs, ft4(1)), amt_domain_field_ptr(outs, ft4(2)),                &
+                                   amt_domain_field_ptr(outs, ft4(3)), amt_domain_field_ptr(outs, ft4(4)))
+    end if
+    call amt_check(rc, 'amt_moments_device')
+    call amt_check(amt_ensemble_sync(ens), 'amt_ensemble_sync')
+    print '(a,i0,a,i0,a)', 'ensemble of ', members, ' members, ', nsweeps, ' sweeps: mean / var / lo / hi of ww, mu and t on the device'
+    do k = 1, 4
+       call amt_check(amt_domain_download(outs, fw(k), c_loc(o3)), 'amt_domain_download')
+       if (k == 1) print '(a,es24.16)', 'checksum of the ensemble-mean ww: ', sum(real(o3, 8))
+       if (len_trim(outdir) > 0) call dump3('ens_ww_'//trim(mname(k)), o3)
+       call amt_check(amt_domain_download(outs, ft4(k), c_loc(o3)), 'amt_domain_download')
+       if (len_trim(outdir) > 0) call dump3('ens_t_'//trim(mname(k)), o3)
+       call amt_check(amt_domain_download(outs, fm(k), c_loc(o2)), 'amt_domain_download')
+       if (len_trim(outdir) > 0) call dump2('ens_mu_'//trim(mname(k)), o2)
+    end do
+    call amt_check(amt_domain_destroy(outs), 'amt_domain_destroy')
+    call amt_check(amt_ensemble_destroy(ens), 'amt_ensemble_destroy')
+  end subroutine
 
   subroutine fill3(field, a)
     integer(c_int), intent(in) :: field

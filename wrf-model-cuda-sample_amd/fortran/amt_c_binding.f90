@@ -988,6 +988,34 @@ MODULE amt_c_binding
          type(c_ptr), value :: handle
          integer(c_int) :: on
       end function
+      ! (13) ensemble mean, sample variance and envelope over the members of a member-stacked field.  Pointer level: a and the
+      ! four outputs are DEVICE pointers; an output of ONE member's extents each, c_null_ptr = not wanted (at least one is);
+      ! asynchronous on hip_stream
+      function amt_moments_device_f32(hip_stream, a, rank, members, ims, ime, jms, jme, kms, kme,                       &
+                                      i0, i1, k0, k1, j0, j1, mean, var, lo, hi) bind(C, name="amt_moments_device_f32") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: hip_stream, a
+         integer(c_int), value :: rank, members, ims, ime, jms, jme, kms, kme, i0, i1, k0, k1, j0, j1
+         type(c_ptr), value :: mean, var, lo, hi
+         integer(c_int) :: rc
+      end function
+      function amt_moments_device_f64(hip_stream, a, rank, members, ims, ime, jms, jme, kms, kme,                       &
+                                      i0, i1, k0, k1, j0, j1, mean, var, lo, hi) bind(C, name="amt_moments_device_f64") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: hip_stream, a
+         integer(c_int), value :: rank, members, ims, ime, jms, jme, kms, kme, i0, i1, k0, k1, j0, j1
+         type(c_ptr), value :: mean, var, lo, hi
+         integer(c_int) :: rc
+      end function
+      ! handle level: region = AMT_REGION_WINDOW or AMT_REGION_MEMORY; asynchronous on the ensemble's stream (amt_ensemble_sync
+      ! waits for it); the outputs are device arrays of one member's extents, e.g. amt_domain_field_ptr of a same-shaped domain
+      function amt_ensemble_moments(handle, field, region, mean, var, lo, hi) bind(C, name="amt_ensemble_moments") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: field, region
+         type(c_ptr), value :: mean, var, lo, hi
+         integer(c_int) :: rc
+      end function
    end interface
 
    ! enum amt_field (include/amt_synth.h): the Fortran argument order

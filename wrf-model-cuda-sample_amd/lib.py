@@ -199,6 +199,9 @@ SYMBOLS = {
     "amt_ensemble_set_guard": (_I, [_P, _I]),
     "amt_domain_guard_report": (_I, [_P, ctypes.POINTER(GuardReport)]),
     "amt_ensemble_guard_report": (_I, [_P, ctypes.POINTER(GuardReport)]),
+    "amt_moments_device_f32": (_I, [_P, _P, _I, _I] + [_I] * 12 + [_P] * 4),
+    "amt_moments_device_f64": (_I, [_P, _P, _I, _I] + [_I] * 12 + [_P] * 4),
+    "amt_ensemble_moments": (_I, [_P, _I, _I] + [_P] * 4),
     "amt_halo_plan": (_I, [_I] * (4 + 17 + 5) + [ctypes.POINTER(HaloMessage), _I, ctypes.POINTER(_I)]),
     "amt_grid_halo_messages": (_I, [_P, ctypes.POINTER(HaloMessage), _I, ctypes.POINTER(_I)]),
     "amt_slab_halo_messages": (_I, [_P, ctypes.POINTER(HaloMessage), _I, ctypes.POINTER(_I)]),
