@@ -270,7 +270,10 @@ int amt_domain_create(amt_domain **out, int dtype_bytes,
  * on the GPU, as WRF's arrays would be): fields[f] is the device pointer of field f (enum
  * amt_field, all AMT_F_COUNT of them, laid out as above); hip_stream is the hipStream_t the
  * handle's work is enqueued on, NULL = a stream of its own.  Nothing is copied; destroy frees
- * neither the arrays nor the caller's stream. */
+ * neither the arrays nor the caller's stream.  Device pointers -- here, in amt_ensemble_wrap and in
+ * every amt_*_device_* call -- need the alignment of their element type only (4 or 8 bytes): arrays
+ * packed back to back in one allocation, at whatever offsets their sizes add up to, are served
+ * (tests/test_gpu_17c_packed_state.py). */
 int amt_domain_wrap(amt_domain **out, int dtype_bytes,
                     int periodic_x, int specified, int nested,
                     int ids, int ide, int jds, int jde, int kde,
