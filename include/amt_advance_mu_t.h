@@ -907,6 +907,77 @@ int amt_moments_device_f64(void *hip_stream, const double *a, int rank, int memb
  * amt_domain_field_stats, amt_domain_compare and amt_domain_download then understand. */
 int amt_ensemble_moments(amt_ensemble *e, int field, int region, void *mean, void *var, void *lo, void *hi);
 
+/* ------------------------------------------------------------------------
+ * (14) The acoustic loop's flux averages ru_m, rv_m, ww_m (WRF's sumflux), on the device.  In solve_em every acoustic
+ *      sub-step runs advance_mu_t, its three spec_bdyupdate calls (12) and then sumflux, which adds the sub-step's u, v and
+ *      ww into three accumulators and, on the last sub-step, turns the sums into the time-averaged mass fluxes that scalar
+ *      advection uses.  Every operand is one of the resident arrays (WRF passes ww1 = ww_1, u_save = u_1, v_save = v_1);
+ *      only the accumulators are new: three arrays of a 3-D field's extents, member-stacked as in (8).
+ *      Indices are Fortran-inclusive and global, on a tile its..ite, jts..jte with kts == 1 and kte == kde; T is the arrays'
+ *      type, n = n_small_steps >= 1 and 1 <= iteration <= n.  Every operation is rounded once in T, there is no fused
+ *      multiply-add, expressions associate left to right as written.  RANGES in which a field accumulates:
+ *        ru_m  adds u    i = its..ite              k = kts..kte-1   j = jts..min(jte, jde-1)
+ *        rv_m  adds v    i = its..min(ite, ide-1)  k = kts..kte-1   j = jts..jte
+ *        ww_m  adds ww   i = its..min(ite, ide-1)  k = kts..kte     j = jts..min(jte, jde-1)
+ *      For a cell of its field's range, x the added field's value there:
+ *        s = (iteration == 1) ? T(0) + x : acc + x      at iteration 1 the old contents of acc are NOT read (they may be NaN);
+ *                                                       T(0) + x makes -0.0 into +0.0, as the Fortran's zero-then-add does
+ *        iteration <  n:  acc = s
+ *        iteration == n:  q = s / T(n) (n converted to T, IEEE divide), and
+ *                           ru_m = q + (muu(i,j) * u_1(i,k,j)) / msfuy(i,j)
+ *                           rv_m = q + (muv(i,j) * v_1(i,k,j)) * msfvx_inv(i,j)
+ *                           ww_m = q + ww_1(i,k,j)
+ *      (n == 1 does both in the one call).  At iteration 1 every cell of the tile box its..ite, kts..kte, jts..jte OUTSIDE a
+ *      field's range becomes +0.0 in that accumulator (WRF zeroes the whole tile); at any other iteration those cells keep
+ *      their bits.  Always bit-unchanged, NaN payloads included: everything outside the tile box, every memory level outside
+ *      kts..kte, every input.  No cell of an input outside the field's range is read (halos may hold NaN), nothing outside
+ *      the arrays is touched.  The result is a function of the operands' contents alone -- not of addresses, alignment,
+ *      stream or launch geometry (no atomics, no workspace).  Inputs may alias one another; an accumulator may not overlap
+ *      any other array of the call.  One launch does a whole accumulation, for every member of an ensemble.
+ *      Reported before any device call, with or without a device, the accumulators untouched:
+ *      AMT_ERR_INVALID_ARG: a NULL array; members < 1; n < 1; iteration outside 1..n; an accumulator that overlaps another
+ *      array.  AMT_ERR_PRECONDITION: the tile outside memory; kts != 1; kte != kde; kme < kte; more than 65535 members.
+ *      NOT provided: the one-shot host-array calls of (1).  A host that owns the arrays accumulates on its own side.
+ * ------------------------------------------------------------------------ */
+/* pointer level, beside amt_advance_mu_t_device_* (members = 1) or amt_advance_mu_t_ensemble_device_*; asynchronous on
+ * hip_stream (NULL = the default stream) */
+int amt_sumflux_device_f32(
+    void *hip_stream, int members, float *ru_m, float *rv_m, float *ww_m,
+    const float *u, const float *v, const float *ww, const float *u_1, const float *v_1, const float *ww_1,
+    const float *muu, const float *muv, const float *msfuy, const float *msfvx_inv,
+    int iteration, int n_small_steps,
+    int ids, int ide, int jds, int jde, int kde,
+    int ims, int ime, int jms, int jme, int kms, int kme,
+    int its, int ite, int jts, int jte, int kts, int kte);
+int amt_sumflux_device_f64(
+    void *hip_stream, int members, double *ru_m, double *rv_m, double *ww_m,
+    const double *u, const double *v, const double *ww, const double *u_1, const double *v_1, const double *ww_1,
+    const double *muu, const double *muv, const double *msfuy, const double *msfvx_inv,
+    int iteration, int n_small_steps,
+    int ids, int ide, int jds, int jde, int kde,
+    int ims, int ime, int jms, int jme, int kms, int kme,
+    int its, int ite, int jts, int jte, int kts, int kte);
+/* n_small_steps = 0: off (the default; the step paths enqueue exactly what they do without this section) and what the
+ * library allocated is freed.  n >= 1 with ru_m, rv_m, ww_m all NULL: the library allocates the three accumulators, each of
+ * one 3-D field's extents (times the members of an ensemble); all three given: the caller's device arrays are used and never
+ * freed; a mix is AMT_ERR_INVALID_ARG.  (The library's own three, as amt_domain_sumflux_ptr returns them, may be handed back to
+ * set n anew: they stay the library's.)  The iteration counter is reset to 1.  Then every sweep of amt_domain_step /
+ * amt_domain_step_timed is followed by one accumulation on the same stream, behind the boundary-zone update of (12) and in
+ * front of the guard's checks of (10); the counter runs 1..n and wraps back to 1.  A handle keeps the setting under
+ * amt_slab_* and amt_grid_*: the accumulation of that rank's own tile is enqueued where the boundary-zone update of (12) is,
+ * in every schedule and in amt_*_step_end; nothing is exchanged for it.  amt_domain_tune_placement neither accumulates nor
+ * advances the counter.  A refusal changes nothing. */
+int amt_domain_set_sumflux(amt_domain *d, int n_small_steps, void *ru_m, void *rv_m, void *ww_m);
+/* one accumulation now, as iteration `next_iteration`, asynchronous on the handle's stream; advances the counter */
+int amt_domain_sumflux_accumulate(amt_domain *d);
+int amt_domain_sumflux_state(const amt_domain *d, int *n, int *next_iteration);   /* n = 0: off; either may be NULL */
+void *amt_domain_sumflux_ptr(amt_domain *d, int which);           /* 0 ru_m, 1 rv_m, 2 ww_m; NULL while off */
+/* the same for an ensemble: all members in one launch, member-stacked accumulators */
+int amt_ensemble_set_sumflux(amt_ensemble *e, int n_small_steps, void *ru_m, void *rv_m, void *ww_m);
+int amt_ensemble_sumflux_accumulate(amt_ensemble *e);
+int amt_ensemble_sumflux_state(const amt_ensemble *e, int *n, int *next_iteration);
+void *amt_ensemble_sumflux_ptr(amt_ensemble *e, int which);
+
 #ifdef __cplusplus
 }
 #endif

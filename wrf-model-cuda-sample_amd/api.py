@@ -153,6 +153,35 @@ def spec_bdy_update(t, ft, mu, muts, mu_tend, dts, config_flags,
     _lib.check(status)
 
 
+def sumflux(ru_m, rv_m, ww_m, u, v, ww, u_1, v_1, ww_1, muu, muv, msfuy, msfvx_inv, iteration, n_small_steps,
+            ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,
+            its, ite, jts, jte, kts, kte, *, members=1, stream=None):
+    """One accumulation of the acoustic loop's flux averages (``amt_sumflux_device_f32/_f64``, header section 14) on a patch's
+    (``members`` > 1: a member-stacked ensemble's) torch device tensors: ``ru_m, rv_m, ww_m`` take ``u, v, ww`` of sub-step
+    ``iteration`` of ``n_small_steps``; the last one turns the sums into the averages.  Asynchronous on ``stream`` (default:
+    torch's current).  Call it behind ``advance_mu_t`` (and ``spec_bdy_update``) on the same stream."""
+    import torch
+    L = _lib.load_library()
+    arrays = (ru_m, rv_m, ww_m, u, v, ww, u_1, v_1, ww_1, muu, muv, msfuy, msfvx_inv)
+    idim, kdim, jdim = ime - ims + 1, kme - kms + 1, jme - jms + 1
+    want = [jdim * kdim * idim] * 9 + [jdim * idim] * 4
+    dt = ru_m.dtype if _is_torch(ru_m) else None
+    if dt not in (torch.float32, torch.float64):
+        raise TypeError(f"unsupported dtype {dt}")
+    for a, n in zip(arrays, want):
+        if not (_is_torch(a) and a.is_cuda and a.dtype == dt and a.is_contiguous() and a.numel() == n * int(members)):
+            raise TypeError("sumflux needs contiguous CUDA tensors of one dtype and of the memory extents")
+    if stream is None:
+        stream = torch.cuda.current_stream(ru_m.device)
+    handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+    fn = L.amt_sumflux_device_f32 if dt == torch.float32 else L.amt_sumflux_device_f64
+    with torch.cuda.device(ru_m.device):
+        status = fn(ctypes.c_void_p(handle), int(members), *[ctypes.c_void_p(a.data_ptr()) for a in arrays],
+                    int(iteration), int(n_small_steps),
+                    *[int(x) for x in (ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte)])
+    _lib.check(status)
+
+
 def advance_mu_t(ww, ww_1, u, u_1, v, v_1, mu, mut, muave, muts, muu, muv, mudf, t, t_1,
                  t_ave, ft, mu_tend, rdx, rdy, dts, epssm, dnw, fnm, fnp, rdnw,
                  msfuy, msfvx_inv, msftx, msfty, config_flags,

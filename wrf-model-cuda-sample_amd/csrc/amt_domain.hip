@@ -11,6 +11,7 @@ extern "C" int amt_domain_destroy(amt_domain *d)
     if (!d) return AMT_OK;
     DeviceScope scope(d->device);
     amt_diag_release(d);
+    amt_sumflux_release(d);
     if (d->owns_fields)
         for (void *&q : d->field)
             if (q) { (void)hipFree(q); q = nullptr; }
@@ -327,6 +328,8 @@ static int amt_domain_step_t(amt_domain *d, int n_sweeps)
         if (rc == AMT_OK) rc = amt_device_call<T>(d->stream, d->variant, a);
         // specified / nested boundaries: the boundary zone is advanced behind the sweep, where WRF has its spec_bdyupdate calls
         if (rc == AMT_OK && d->spec_bdy) rc = amt_bdy_update_domain("amt_domain_step", d, 1);
+        // the acoustic loop's flux averages: one accumulation behind the boundary-zone update, where WRF has its sumflux call
+        if (rc == AMT_OK && d->sumflux_n) rc = amt_sumflux_accumulate_domain("amt_domain_step", d, 1);
         if (rc == AMT_OK && d->guard_every) rc = amt_diag_after_sweep("amt_domain_step", d, 1);
         if (rc) return rc;
     }
@@ -402,12 +405,15 @@ static int amt_domain_tune(amt_domain *d, int tries, float *ms_per_try, bool pre
 {
     DeviceScope scope(d->device);
     // the timed sweeps are scaffolding: an armed non-finite guard neither checks nor counts them (and does not stretch them)
-    // nor does the boundary-zone update follow them
+    // nor does the boundary-zone update follow them, nor a flux accumulation (its counter and accumulators stay as they are)
     struct StepExtrasPause {
         amt_domain *d;
-        int every, spec_bdy;
-        explicit StepExtrasPause(amt_domain *dom) : d(dom), every(dom->guard_every), spec_bdy(dom->spec_bdy) { d->guard_every = 0; d->spec_bdy = 0; }
-        ~StepExtrasPause() { d->guard_every = every; d->spec_bdy = spec_bdy; }
+        int every, spec_bdy, sumflux_n;
+        explicit StepExtrasPause(amt_domain *dom) : d(dom), every(dom->guard_every), spec_bdy(dom->spec_bdy), sumflux_n(dom->sumflux_n)
+        {
+            d->guard_every = 0; d->spec_bdy = 0; d->sumflux_n = 0;
+        }
+        ~StepExtrasPause() { d->guard_every = every; d->spec_bdy = spec_bdy; d->sumflux_n = sumflux_n; }
     } pause(d);
     auto bytes = [&](int f) { return d->count(f) * (size_t)d->dtype_bytes; };
     auto time_current = [&](float *ms) -> int {

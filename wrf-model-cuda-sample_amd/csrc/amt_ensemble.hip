@@ -21,6 +21,7 @@ extern "C" int amt_ensemble_destroy(amt_ensemble *e)
     amt_domain &d = e->d;
     DeviceScope scope(d.device);
     amt_diag_release(&d);
+    amt_sumflux_release(&d);
     if (d.owns_fields)
         for (void *&q : d.field)
             if (q) { (void)hipFree(q); q = nullptr; }
@@ -178,6 +179,8 @@ static int amt_ensemble_step_t(amt_ensemble *e, int n_sweeps)
         if (rc == AMT_OK) rc = amt_device_call_ensemble<T>(e->d.stream, e->d.variant, e->members, a);
         // specified / nested boundaries: every member's boundary zone in one launch behind the sweep
         if (rc == AMT_OK && e->d.spec_bdy) rc = amt_bdy_update_domain("amt_ensemble_step", &e->d, e->members);
+        // the flux averages: every member's accumulation in one launch behind the boundary-zone update
+        if (rc == AMT_OK && e->d.sumflux_n) rc = amt_sumflux_accumulate_domain("amt_ensemble_step", &e->d, e->members);
         if (rc == AMT_OK && e->d.guard_every) rc = amt_diag_after_sweep("amt_ensemble_step", &e->d, e->members);
         if (rc) return rc;
     }

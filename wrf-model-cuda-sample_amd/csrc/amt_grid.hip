@@ -149,7 +149,13 @@ int grid_tile(amt_grid *g, hipStream_t stream, int its, int ite, int jts, int jt
 // Specified / nested boundaries (amt_domain_set_spec_bdy): the boundary-zone update of this rank's own
 // tile, on the domain's stream where the sweep's work has joined it.  The zone holds outputs only: nothing is exchanged for it,
 // and a patch that touches no domain edge enqueues nothing.
-int grid_bdy(amt_grid *g, const char *who) { return g->dom->spec_bdy ? amt_bdy_update_domain(who, g->dom, 1) : AMT_OK; }
+// With amt_domain_set_sumflux the flux accumulation of this rank's own tile follows at the same place:
+// its operands are this rank's u, v and the ww the sweep has just written, nothing is exchanged for it either.
+int grid_bdy(amt_grid *g, const char *who)
+{
+    const int rc = g->dom->spec_bdy ? amt_bdy_update_domain(who, g->dom, 1) : AMT_OK;
+    return rc == AMT_OK && g->dom->sumflux_n ? amt_sumflux_accumulate_domain(who, g->dom, 1) : rc;
+}
 
 // the cells that read a neighbour's data, after the halos are in: boundary rows over the patch's whole width (they own the
 // corners), boundary columns over the rows in between; every tile is clipped on its own by the routine's window rule

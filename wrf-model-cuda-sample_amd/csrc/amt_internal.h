@@ -190,6 +190,10 @@ struct amt_domain {
     float placement_ms[16] = {};  // sweep time on each (0: not tried)
     int guard_every = 0;          // non-finite guard: check after every n-th sweep (amt_domain_set_guard); 0 = off
     AmtDiagState *diag = nullptr; // made by the first call of section (10) on this handle, freed with it
+    int sumflux_n = 0;            // n_small_steps: one flux accumulation follows every sweep (amt_domain_set_sumflux); 0 = off
+    int sumflux_next = 1;         // the iteration the next accumulation is, 1..sumflux_n
+    void *sumflux_acc[3] = {};    // ru_m, rv_m, ww_m: one 3-D field's extents each (times the members of an ensemble)
+    bool sumflux_owned = false;   // true: allocated by the library, freed with the setting or the handle
     size_t count(int f) const
     {
         const size_t idim = ime - ims + 1, kdim = kme - kms + 1, jdim = jme - jms + 1;
@@ -231,6 +235,18 @@ int amt_cyclic_check_domain(const char *who, const amt_domain *d, int axes, int 
 // ---------------------------------------------------------------------------
 int amt_bdy_update_domain(const char *who, amt_domain *d, int members);
 int amt_bdy_check_domain(const char *who, const amt_domain *d, int members);
+
+// ---------------------------------------------------------------------------
+// the acoustic loop's flux averages (amt_sumflux.hip, header section 14).  The steppers call amt_sumflux_accumulate_domain
+// only while the setting is on (d->sumflux_n != 0): with it off they enqueue what they always did.
+//   amt_sumflux_accumulate_domain: one accumulation of `members` member-stacked patches of the domain's shape on the domain's
+//                                  stream, as iteration d->sumflux_next, which then advances 1..n and wraps
+//   amt_sumflux_set_domain:        amt_*_set_sumflux (n = 0: off); a refusal changes nothing
+//   amt_sumflux_release:           turns the setting off and frees what the library allocated (the handles' destroy)
+// ---------------------------------------------------------------------------
+int amt_sumflux_accumulate_domain(const char *who, amt_domain *d, int members);
+int amt_sumflux_set_domain(const char *who, amt_domain *d, int members, int n, void *ru_m, void *rv_m, void *ww_m);
+void amt_sumflux_release(amt_domain *d);
 
 // ---------------------------------------------------------------------------
 // field statistics, comparison and the non-finite guard (amt_diag.hip, header section 10).  The steppers call these only

@@ -1,0 +1,357 @@
+// amt_sumflux.hip -- the acoustic loop's flux averages on the device (include/amt_advance_mu_t.h section 14, DESIGN.md
+// section 7.7).  In WRF's solve_em every acoustic sub-step ends with sumflux: u, v and ww of the sub-step are added into the
+// time-averaged mass fluxes ru_m, rv_m, ww_m, and the last sub-step turns the sums into the averages that scalar advection uses:
+//   s = (iteration == 1) ? 0 + x : acc + x;      iteration < n:  acc = s
+//   iteration == n, q = s / n:   ru_m = q + (muu * u_1) / msfuy;   rv_m = q + (muv * v_1) * msfvx_inv;   ww_m = q + ww_1
+// every operation rounded once in the arrays' type (the library is built with -ffp-contract=off).  Each accumulator has its
+// own range inside the tile box its..ite, kts..kte, jts..jte (ru_m: all of i, rv_m: all of j, ww_m: all of k; otherwise
+// one short of the domain's end); at iteration 1 the tile's cells outside it become +0.0.  ONE launch does the three
+// accumulators, times the members of an ensemble.  A separate streaming pass behind the sweep: the march kernel is not touched.
+#include "amt_internal.h"
+
+namespace {
+enum { AMT_SUMFLUX_JOBS = 3 };              // ru_m, rv_m, ww_m
+
+// Job q works on the tile box of its accumulator: nk * nj runs of `ni` contiguous elements, run r = (k, j) = (r % nk, r / nk)
+// of member m starting at element m * mstride3 + j * jstride3 + k * idim + first3 of acc, x and x1 alike (the three 3-D arrays
+// of a job have one layout) and at m * mstride2 + j * idim + first2 of the two 2-D factors.  Element (i, k, j) of the box is
+// in the accumulator's range when i < ilen[q], k < klen[q] and j < jlen[q].
+template <typename T>
+struct AmtSumfluxJobs {
+    T *acc[AMT_SUMFLUX_JOBS];
+    const T *x[AMT_SUMFLUX_JOBS], *x1[AMT_SUMFLUX_JOBS];
+    const T *fa[AMT_SUMFLUX_JOBS], *fb[AMT_SUMFLUX_JOBS];          // muu, msfuy / muv, msfvx_inv / none
+    int ilen[AMT_SUMFLUX_JOBS], klen[AMT_SUMFLUX_JOBS], jlen[AMT_SUMFLUX_JOBS];
+    int ni, nk, nj;
+    long idim, jstride3, mstride3, mstride2, first3, first2;
+    T n;                                                           // n_small_steps in the arrays' type
+    int first, last;                                               // iteration == 1, iteration == n
+};
+
+template <typename T> struct AmtSumfluxVec;
+template <> struct AmtSumfluxVec<float> { typedef float type __attribute__((ext_vector_type(4))); };
+template <> struct AmtSumfluxVec<double> { typedef double type __attribute__((ext_vector_type(2))); };
+
+// what the last sub-step adds to the average: job 0 (muu * u_1) / msfuy, job 1 (muv * v_1) * msfvx_inv, job 2 ww_1
+template <typename T>
+__device__ __forceinline__ T amt_sumflux_base(int q, T x1, T fa, T fb)
+{
+    if (q == 2) return x1;
+    const T p = fa * x1;
+    return q == 0 ? p / fb : p * fb;
+}
+
+// Grid (blocks, 3 jobs, members).  A work item is one 16-byte chunk of a run (its last chunk may be short), lanes run along
+// (chunk, k, j): along i first, so that every stream of a wave is coalesced.  A whole chunk inside the range moves as ONE
+// 16-byte access per 3-D stream where all of them lie on a 16-byte boundary (decided per chunk from its addresses, behind the
+// member offset); a run's short last chunk, a chunk that holds the cell past the range and every other chunk go element by
+// element.  The 2-D factors are loaded at the last iteration only.  A run outside the range in k or j, and the cell past it in
+// i, is zeroed at the first iteration and not touched otherwise.  The arithmetic is the same on both paths.
+// Nothing outside the tile box is read or written.  Offsets are 64-bit.  256 threads, no LDS.
+template <typename T>
+__global__ __launch_bounds__(256) void amt_sumflux_kernel(AmtSumfluxJobs<T> jobs)
+{
+    typedef typename AmtSumfluxVec<T>::type V;
+    constexpr int kPer = 16 / (int)sizeof(T);
+    const int q = blockIdx.y;
+    const long moff3 = (long)blockIdx.z * jobs.mstride3 + jobs.first3, moff2 = (long)blockIdx.z * jobs.mstride2 + jobs.first2;
+    T *acc = jobs.acc[q] + moff3;
+    const T *x = jobs.x[q] + moff3, *x1 = jobs.x1[q] + moff3;
+    const T *fa = q == 2 ? nullptr : jobs.fa[q] + moff2, *fb = q == 2 ? nullptr : jobs.fb[q] + moff2;
+    const bool first = jobs.first != 0, last = jobs.last != 0;
+    const T n = jobs.n;
+    const long ni = jobs.ni, nk = jobs.nk, ilen = jobs.ilen[q];
+    const int klen = jobs.klen[q], jlen = jobs.jlen[q];
+    const long chunks = (ni + kPer - 1) / kPer;
+    const long total = nk * (long)jobs.nj * chunks;
+    const bool narrow = total <= 0x7fffffffL;                      // wave-uniform: 32-bit divisions where they suffice
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        long r, j;
+        if (narrow) {
+            r = (long)((unsigned)e / (unsigned)chunks);
+            j = (long)((unsigned)r / (unsigned)nk);
+        } else {
+            r = e / chunks;
+            j = r / nk;
+        }
+        const long k = r - j * nk;
+        const long i0 = (e - r * chunks) * kPer;                   // first element of this chunk inside its run
+        const long at3 = j * jobs.jstride3 + k * jobs.idim + i0, at2 = j * jobs.idim + i0;
+        const long left = ni - i0;
+        const int cnt = left < kPer ? (int)left : kPer;
+        T *a = acc + at3;
+        if (k >= klen || j >= jlen) {                              // a run of the tile outside the accumulator's range
+            if (first) {
+                if (cnt == kPer && (reinterpret_cast<uintptr_t>(a) & 15) == 0) {
+                    V z;
+                    for (int i = 0; i < kPer; ++i) z[i] = T(0);
+                    *reinterpret_cast<V *>(a) = z;
+                } else {
+                    for (int i = 0; i < cnt; ++i) a[i] = T(0);
+                }
+            }
+            continue;
+        }
+        const T *xs = x + at3, *x1s = x1 + at3;
+        uintptr_t bits = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(xs);
+        if (last) bits |= reinterpret_cast<uintptr_t>(x1s);
+        if (cnt == kPer && i0 + kPer <= ilen && (bits & 15) == 0) {
+            V s = *reinterpret_cast<const V *>(xs);
+            if (first) {
+                for (int i = 0; i < kPer; ++i) s[i] = T(0) + s[i];
+            } else {
+                const V old = *reinterpret_cast<const V *>(a);
+                for (int i = 0; i < kPer; ++i) s[i] = old[i] + s[i];
+            }
+            if (last) {
+                const V b = *reinterpret_cast<const V *>(x1s);
+                for (int i = 0; i < kPer; ++i) {
+                    const T f0 = q == 2 ? T(0) : fa[at2 + i], f1 = q == 2 ? T(0) : fb[at2 + i];
+                    const T avg = s[i] / n;
+                    s[i] = avg + amt_sumflux_base<T>(q, b[i], f0, f1);
+                }
+            }
+            *reinterpret_cast<V *>(a) = s;
+        } else {
+            for (int i = 0; i < cnt; ++i) {
+                if (i0 + i >= ilen) {                              // the tile's cell past the range in i
+                    if (first) a[i] = T(0);
+                    continue;
+                }
+                T s = first ? T(0) + xs[i] : a[i] + xs[i];
+                if (last) {
+                    const T f0 = q == 2 ? T(0) : fa[at2 + i], f1 = q == 2 ? T(0) : fb[at2 + i];
+                    const T avg = s / n;
+                    s = avg + amt_sumflux_base<T>(q, x1s[i], f0, f1);
+                }
+                a[i] = s;
+            }
+        }
+    }
+}
+
+struct SumfluxArrays {
+    void *ru_m, *rv_m, *ww_m;
+    const void *u, *v, *ww, *u_1, *v_1, *ww_1, *muu, *muv, *msfuy, *msfvx_inv;
+};
+
+// Argument and precondition checks: host arithmetic only.  *empty: the tile box holds no cell (nothing to do).
+int sumflux_check(const char *who, const amt_domain &s, int members, const SumfluxArrays &a, int iteration, int n, bool *empty)
+{
+    *empty = false;
+    if (!a.ru_m || !a.rv_m || !a.ww_m || !a.u || !a.v || !a.ww || !a.u_1 || !a.v_1 || !a.ww_1 || !a.muu || !a.muv || !a.msfuy || !a.msfvx_inv)
+        return amt_fail(AMT_ERR_INVALID_ARG, "%s: null array pointer", who);
+    if (members < 1) return amt_fail(AMT_ERR_INVALID_ARG, "%s: members = %d: an ensemble has at least one member", who, members);
+    if (n < 1) return amt_fail(AMT_ERR_INVALID_ARG, "%s: n_small_steps = %d: an acoustic loop has at least one sub-step", who, n);
+    if (iteration < 1 || iteration > n) return amt_fail(AMT_ERR_INVALID_ARG, "%s: iteration %d is not in 1..%d", who, iteration, n);
+    if (s.ime < s.ims || s.jme < s.jms || s.kme < s.kms) return amt_fail(AMT_ERR_PRECONDITION, "%s: empty memory extents", who);
+    // an accumulator may overlap no other array of the call (the inputs may alias one another)
+    const size_t idim = s.ime - s.ims + 1, kdim = s.kme - s.kms + 1, jdim = s.jme - s.jms + 1;
+    const size_t b3 = idim * kdim * jdim * (size_t)members * (size_t)s.dtype_bytes, b2 = idim * jdim * (size_t)members * (size_t)s.dtype_bytes;
+    const void *acc[3] = {a.ru_m, a.rv_m, a.ww_m};
+    const void *in[10] = {a.u, a.v, a.ww, a.u_1, a.v_1, a.ww_1, a.muu, a.muv, a.msfuy, a.msfvx_inv};
+    auto overlap = [](const void *p, size_t pb, const void *r, size_t rb) {
+        const uintptr_t p0 = reinterpret_cast<uintptr_t>(p), r0 = reinterpret_cast<uintptr_t>(r);
+        return p0 < r0 + rb && r0 < p0 + pb;
+    };
+    for (int k = 0; k < 3; ++k) {
+        for (int m = k + 1; m < 3; ++m)
+            if (overlap(acc[k], b3, acc[m], b3)) return amt_fail(AMT_ERR_INVALID_ARG, "%s: two accumulators overlap", who);
+        for (int m = 0; m < 10; ++m)
+            if (overlap(acc[k], b3, in[m], m < 6 ? b3 : b2)) return amt_fail(AMT_ERR_INVALID_ARG, "%s: an accumulator overlaps an input array", who);
+    }
+    if (s.kts != 1) return amt_fail(AMT_ERR_PRECONDITION, "%s: kts = %d, the library needs kts == 1", who, s.kts);
+    if (s.kte != s.kde) return amt_fail(AMT_ERR_PRECONDITION, "%s: kte = %d is not kde = %d", who, s.kte, s.kde);
+    if (s.kme < s.kte || s.kms > s.kts) return amt_fail(AMT_ERR_PRECONDITION, "%s: levels kts:kte = %d:%d are not inside memory kms:kme = %d:%d", who, s.kts, s.kte, s.kms, s.kme);
+    if (s.ite < s.its || s.jte < s.jts || s.kte < s.kts) { *empty = true; return AMT_OK; }
+    if (s.its < s.ims || s.ite > s.ime || s.jts < s.jms || s.jte > s.jme)
+        return amt_fail(AMT_ERR_PRECONDITION, "%s: the tile %d:%d, %d:%d is not inside memory %d:%d, %d:%d", who,
+                        s.its, s.ite, s.jts, s.jte, s.ims, s.ime, s.jms, s.jme);
+    if (members > 65535) return amt_fail(AMT_ERR_PRECONDITION, "%s: %d members: one launch covers at most 65535", who, members);
+    return AMT_OK;
+}
+
+template <typename T>
+int sumflux_launch(const amt_domain &d, int members, const SumfluxArrays &a, int iteration, int n)
+{
+    const long idim = d.ime - d.ims + 1, kdim = d.kme - d.kms + 1, jdim = d.jme - d.jms + 1;
+    AmtSumfluxJobs<T> jobs{};
+    jobs.acc[0] = static_cast<T *>(a.ru_m); jobs.x[0] = static_cast<const T *>(a.u); jobs.x1[0] = static_cast<const T *>(a.u_1);
+    jobs.acc[1] = static_cast<T *>(a.rv_m); jobs.x[1] = static_cast<const T *>(a.v); jobs.x1[1] = static_cast<const T *>(a.v_1);
+    jobs.acc[2] = static_cast<T *>(a.ww_m); jobs.x[2] = static_cast<const T *>(a.ww); jobs.x1[2] = static_cast<const T *>(a.ww_1);
+    jobs.fa[0] = static_cast<const T *>(a.muu); jobs.fb[0] = static_cast<const T *>(a.msfuy);
+    jobs.fa[1] = static_cast<const T *>(a.muv); jobs.fb[1] = static_cast<const T *>(a.msfvx_inv);
+    jobs.ni = d.ite - d.its + 1; jobs.nk = d.kte - d.kts + 1; jobs.nj = d.jte - d.jts + 1;
+    const int imass = (d.ite < d.ide - 1 ? d.ite : d.ide - 1) - d.its + 1;     // may be <= 0: no cell of the range
+    const int jmass = (d.jte < d.jde - 1 ? d.jte : d.jde - 1) - d.jts + 1;
+    jobs.ilen[0] = jobs.ni; jobs.klen[0] = jobs.nk - 1; jobs.jlen[0] = jmass;
+    jobs.ilen[1] = imass;   jobs.klen[1] = jobs.nk - 1; jobs.jlen[1] = jobs.nj;
+    jobs.ilen[2] = imass;   jobs.klen[2] = jobs.nk;     jobs.jlen[2] = jmass;
+    jobs.idim = idim; jobs.jstride3 = kdim * idim; jobs.mstride3 = idim * kdim * jdim; jobs.mstride2 = idim * jdim;
+    jobs.first3 = ((long)(d.jts - d.jms) * kdim + (d.kts - d.kms)) * idim + (d.its - d.ims);
+    jobs.first2 = (long)(d.jts - d.jms) * idim + (d.its - d.ims);
+    jobs.n = (T)n;
+    jobs.first = iteration == 1; jobs.last = iteration == n;
+    constexpr long per = 16 / (long)sizeof(T);
+    const long total = (long)jobs.nk * jobs.nj * ((jobs.ni + per - 1) / per);
+    long blocks = (total + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(amt_sumflux_kernel<T>, dim3((unsigned)blocks, AMT_SUMFLUX_JOBS, (unsigned)members), dim3(256), 0, d.stream, jobs);
+    AMT_HIP(hipGetLastError());
+    return AMT_OK;
+}
+
+// the checks, then the launch.  with_device_check: the pointer-level calls, which may be the first HIP call of a process,
+// report a missing device themselves -- behind the argument errors, which need none
+int sumflux_run(const char *who, const amt_domain &d, int members, const SumfluxArrays &a, int iteration, int n, bool with_device_check)
+{
+    bool empty = false;
+    const int rc = sumflux_check(who, d, members, a, iteration, n, &empty);
+    if (rc != AMT_OK || empty) return rc;
+    if (with_device_check) {
+        int ndev = 0;
+        AMT_HIP(hipGetDeviceCount(&ndev));
+        if (ndev < 1) return amt_fail(AMT_ERR_NO_DEVICE, "no HIP device visible");
+    }
+    return d.dtype_bytes == 8 ? sumflux_launch<double>(d, members, a, iteration, n) : sumflux_launch<float>(d, members, a, iteration, n);
+}
+
+SumfluxArrays sumflux_of_domain(const amt_domain *d)
+{
+    return SumfluxArrays{d->sumflux_acc[0], d->sumflux_acc[1], d->sumflux_acc[2], d->field[AMT_F_U], d->field[AMT_F_V], d->field[AMT_F_WW],
+                         d->field[AMT_F_U_1], d->field[AMT_F_V_1], d->field[AMT_F_WW_1], d->field[AMT_F_MUU], d->field[AMT_F_MUV],
+                         d->field[AMT_F_MSFUY], d->field[AMT_F_MSFVX_INV]};
+}
+}  // namespace
+
+// what the handles and the steppers call: one accumulation of `members` member-stacked patches of the domain's shape, on the
+// domain's stream; the counter goes 1..n and wraps.  Off (n == 0): AMT_ERR_INVALID_ARG.
+int amt_sumflux_accumulate_domain(const char *who, amt_domain *d, int members)
+{
+    if (d->sumflux_n < 1) return amt_fail(AMT_ERR_INVALID_ARG, "%s: the flux averages are off (amt_*_set_sumflux)", who);
+    const int rc = sumflux_run(who, *d, members, sumflux_of_domain(d), d->sumflux_next, d->sumflux_n, false);
+    if (rc == AMT_OK) d->sumflux_next = d->sumflux_next == d->sumflux_n ? 1 : d->sumflux_next + 1;
+    return rc;
+}
+
+void amt_sumflux_release(amt_domain *d)
+{
+    for (void *&q : d->sumflux_acc) {
+        if (q && d->sumflux_owned) (void)hipFree(q);
+        q = nullptr;
+    }
+    d->sumflux_n = 0;
+    d->sumflux_next = 1;
+    d->sumflux_owned = false;
+}
+
+// amt_*_set_sumflux.  A refusal changes nothing.
+int amt_sumflux_set_domain(const char *who, amt_domain *d, int members, int n, void *ru_m, void *rv_m, void *ww_m)
+{
+    if (n < 0) return amt_fail(AMT_ERR_INVALID_ARG, "%s: n_small_steps = %d", who, n);
+    if (n == 0) { amt_sumflux_release(d); return AMT_OK; }
+    const int given = (ru_m != nullptr) + (rv_m != nullptr) + (ww_m != nullptr);
+    if (given != 0 && given != 3)
+        return amt_fail(AMT_ERR_INVALID_ARG, "%s: give all three accumulators or none (the library then allocates them)", who);
+    void *acc[3] = {ru_m, rv_m, ww_m};
+    const size_t bytes = d->count(AMT_F_WW) * (size_t)members * (size_t)d->dtype_bytes;
+    // the library's own arrays handed back (amt_*_sumflux_ptr): they stay the library's, n and the counter are set anew;
+    // one or two of them among the caller's would be freed under the caller
+    const bool same = given == 3 && d->sumflux_owned && memcmp(acc, d->sumflux_acc, sizeof acc) == 0;
+    if (given == 3 && d->sumflux_owned && !same)
+        for (void *mine : d->sumflux_acc)
+            for (void *theirs : acc)
+                if (mine == theirs) return amt_fail(AMT_ERR_INVALID_ARG, "%s: an accumulator the library allocated, mixed with others", who);
+    if (given == 3) {
+        amt_domain probe = *d;                                     // the checks against the caller's arrays, nothing enqueued
+        memcpy(probe.sumflux_acc, acc, sizeof acc);
+        bool empty = false;
+        const int rc = sumflux_check(who, probe, members, sumflux_of_domain(&probe), 1, n, &empty);
+        if (rc) return rc;
+    } else {
+        if (members > 65535) return amt_fail(AMT_ERR_PRECONDITION, "%s: %d members: one launch covers at most 65535", who, members);
+        if (d->kts != 1 || d->kte != d->kde || d->kme < d->kte || d->kms > d->kts || d->its < d->ims || d->ite > d->ime || d->jts < d->jms || d->jte > d->jme)
+            return amt_fail(AMT_ERR_PRECONDITION, "%s: the handle's tile does not admit the flux averages (kts == 1, kte == kde, tile inside memory)", who);
+        for (int k = 0; k < 3; ++k) {
+            acc[k] = nullptr;
+            if (hipMalloc(&acc[k], bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                for (int m = 0; m < k; ++m) (void)hipFree(acc[m]);
+                return amt_fail(AMT_ERR_ALLOC, "%s: no room for three arrays of %zu bytes", who, bytes);
+            }
+        }
+    }
+    if (!same) {
+        amt_sumflux_release(d);
+        memcpy(d->sumflux_acc, acc, sizeof acc);
+        d->sumflux_owned = given == 0;
+    }
+    d->sumflux_n = n;
+    d->sumflux_next = 1;
+    return AMT_OK;
+}
+
+#define AMT_SUMFLUX_SIG(T)                                                                                     \
+    void *hip_stream, int members, T *ru_m, T *rv_m, T *ww_m, const T *u, const T *v, const T *ww,             \
+    const T *u_1, const T *v_1, const T *ww_1, const T *muu, const T *muv, const T *msfuy, const T *msfvx_inv, \
+    int iteration, int n_small_steps, int ids, int ide, int jds, int jde, int kde,                             \
+    int ims, int ime, int jms, int jme, int kms, int kme, int its, int ite, int jts, int jte, int kts, int kte
+#define AMT_SUMFLUX_BODY(T, name)                                                                              \
+    amt_domain d{(int)sizeof(T), 0, 0, 0, ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte}; \
+    d.stream = static_cast<hipStream_t>(hip_stream);                                                           \
+    return sumflux_run(name, d, members, SumfluxArrays{ru_m, rv_m, ww_m, u, v, ww, u_1, v_1, ww_1, muu, muv, msfuy, msfvx_inv}, \
+                       iteration, n_small_steps, true);
+
+extern "C" int amt_sumflux_device_f32(AMT_SUMFLUX_SIG(float)) { AMT_SUMFLUX_BODY(float, "amt_sumflux_device_f32") }
+extern "C" int amt_sumflux_device_f64(AMT_SUMFLUX_SIG(double)) { AMT_SUMFLUX_BODY(double, "amt_sumflux_device_f64") }
+
+// ---- the handles -------------------------------------------------------------------------------------------------------
+extern "C" int amt_domain_set_sumflux(amt_domain *d, int n_small_steps, void *ru_m, void *rv_m, void *ww_m)
+{
+    if (!d) return amt_fail(AMT_ERR_INVALID_ARG, "null domain");
+    DeviceScope scope(d->device);
+    return amt_sumflux_set_domain("amt_domain_set_sumflux", d, 1, n_small_steps, ru_m, rv_m, ww_m);
+}
+
+extern "C" int amt_domain_sumflux_accumulate(amt_domain *d)
+{
+    if (!d) return amt_fail(AMT_ERR_INVALID_ARG, "null domain");
+    DeviceScope scope(d->device);
+    return amt_sumflux_accumulate_domain("amt_domain_sumflux_accumulate", d, 1);
+}
+
+extern "C" int amt_domain_sumflux_state(const amt_domain *d, int *n, int *next_iteration)
+{
+    if (!d) return amt_fail(AMT_ERR_INVALID_ARG, "null domain");
+    if (n) *n = d->sumflux_n;
+    if (next_iteration) *next_iteration = d->sumflux_next;
+    return AMT_OK;
+}
+
+extern "C" void *amt_domain_sumflux_ptr(amt_domain *d, int which)
+{
+    if (!d || which < 0 || which > 2) return nullptr;
+    return d->sumflux_acc[which];
+}
+
+extern "C" int amt_ensemble_set_sumflux(amt_ensemble *e, int n_small_steps, void *ru_m, void *rv_m, void *ww_m)
+{
+    if (!e) return amt_fail(AMT_ERR_INVALID_ARG, "null ensemble");
+    DeviceScope scope(e->d.device);
+    return amt_sumflux_set_domain("amt_ensemble_set_sumflux", &e->d, e->members, n_small_steps, ru_m, rv_m, ww_m);
+}
+
+extern "C" int amt_ensemble_sumflux_accumulate(amt_ensemble *e)
+{
+    if (!e) return amt_fail(AMT_ERR_INVALID_ARG, "null ensemble");
+    DeviceScope scope(e->d.device);
+    return amt_sumflux_accumulate_domain("amt_ensemble_sumflux_accumulate", &e->d, e->members);
+}
+
+extern "C" int amt_ensemble_sumflux_state(const amt_ensemble *e, int *n, int *next_iteration)
+{
+    if (!e) return amt_fail(AMT_ERR_INVALID_ARG, "null ensemble");
+    return amt_domain_sumflux_state(&e->d, n, next_iteration);
+}
+
+extern "C" void *amt_ensemble_sumflux_ptr(amt_ensemble *e, int which) { return e ? amt_domain_sumflux_ptr(&e->d, which) : nullptr; }

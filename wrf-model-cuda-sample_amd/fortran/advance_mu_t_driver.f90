@@ -9,11 +9,13 @@
 ! domain handle (device arrays kept across calls -- the kernel-only time the
 ! reference reports) and checks that both paths agree bit for bit.
 !
-!   advance_mu_t_driver [NI NK NJ [nsweeps [outdir [flags [placements [members]]]]]]
+!   advance_mu_t_driver [NI NK NJ [nsweeps [outdir [flags [placements [members [nsmall]]]]]]]
 !     flags: 0 none, 1 specified, 2 nested, 3 specified+periodic_x
 !     placements: > 1 samples that many allocations of the resident state and keeps the fastest (amt_domain_tune_placement)
 !     members: > 0 adds an ensemble of that many members of the same shape (amt_ensemble_fill_synthetic, seeds seed + m),
 !              stepped nsweeps times, and its mean / variance / envelope over the members (header section 13)
+!     nsmall: > 0 adds an acoustic loop of that many sub-steps on a resident handle with the flux averages ru_m, rv_m, ww_m
+!             accumulated on the device behind every sweep (header section 14), on a single patch and on an ensemble
 !   With outdir the 7 updated arrays are written there as raw native-endian
 !   streams <name>.bin for an external checker; with members the moments as ens_<field>_<mean|var|lo|hi>.bin:
 !   ww over the whole memory, mu over the compute window, t over the memory less one cell on every side (zero outside).
@@ -42,7 +44,7 @@ program advance_mu_t_driver
   real(c_float) :: ms
   integer(kind=8) :: c0, c1, cmid, hz
   real(kind=8) :: cells, secs
-  integer :: nbad, ndef, ntune, members
+  integer :: nbad, ndef, ntune, members, nsmall
   integer(c_int) :: nslots, slot_ids(16)
   real(c_float) :: tune_ms(8)
 
@@ -67,6 +69,10 @@ program advance_mu_t_driver
   members = 0
   if (command_argument_count() >= 8) then
      call get_command_argument(8, arg); read (arg, *) members
+  end if
+  nsmall = 0
+  if (command_argument_count() >= 9) then
+     call get_command_argument(9, arg); read (arg, *) nsmall
   end if
   config_flags%specified  = (iflag == 1 .or. iflag == 3)
   config_flags%nested     = (iflag == 2)
@@ -271,8 +277,110 @@ program advance_mu_t_driver
   if (ndef /= 0) error stop 5
 
   if (members > 0) call ensemble_moments()
+  if (nsmall > 0) call flux_averages()
 
 contains
+
+  ! One acoustic loop of nsmall sub-steps with the flux averages kept on the device: the handle accumulates behind every sweep
+  ! into arrays the library allocates; the same loop is then repeated with the pointer-level call into caller-owned arrays (the
+  ! 3-D fields of a second handle of the same shape serve, and come down with amt_domain_download), and on an ensemble.
+  subroutine flux_averages()
+    type(c_ptr) :: d, e, outs, stream
+    real(wp), allocatable, target :: o3(:,:,:)
+    integer(c_int) :: wb, px, sp, ne, n, nxt, mm, it, acc(3)
+    character(len=4), parameter :: aname(3) = ['ru_m', 'rv_m', 'ww_m']
+    integer :: k
+    wb = int(storage_size(rdx)/8, c_int)
+    px = merge(1_c_int, 0_c_int, config_flags%periodic_x)
+    sp = merge(1_c_int, 0_c_int, config_flags%specified)
+    ne = merge(1_c_int, 0_c_int, config_flags%nested)
+    mm = int(max(members, 1), c_int)
+    acc = [AMT_F_T, AMT_F_T_AVE, AMT_F_FT]                      ! the caller-owned accumulators: three 3-D arrays of `outs`
+    allocate (o3(ims:ime,kms:kme,jms:jme))
+    call amt_check(amt_domain_create(d, wb, px, sp, ne, ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,             &
+                                     its, ite, jts, jte, kts, kte), 'amt_domain_create')
+    call amt_check(amt_domain_create(outs, wb, px, sp, ne, ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,          &
+                                     its, ite, jts, jte, kts, kte), 'amt_domain_create')
+    call amt_check(amt_domain_set_scalars(d, real(rdx, c_double), real(rdy, c_double), real(dts, c_double),              &
+                                          real(epssm, c_double)), 'amt_domain_set_scalars')
+    call amt_check(amt_domain_fill_synthetic(d, seed, int(ims, c_long), int(kms-1, c_long), int(jms, c_long),            &
+                   int(ni+2, c_long), int(nk+1, c_long), int(nj+2, c_long)), 'amt_domain_fill_synthetic')
+    o3 = 0.0_wp                                                 ! what a cell outside the tile box keeps
+    do k = 1, 3
+       call amt_check(amt_domain_upload(outs, acc(k), c_loc(o3)), 'amt_domain_upload')
+    end do
+    ! handle level, library-owned accumulators: one accumulation behind every sweep, the counter wraps after nsmall
+    call amt_check(amt_domain_set_sumflux(d, int(nsmall, c_int), c_null_ptr, c_null_ptr, c_null_ptr), 'amt_domain_set_sumflux')
+    call amt_check(amt_domain_step(d, int(nsmall, c_int)), 'amt_domain_step')
+    call amt_check(amt_domain_sumflux_state(d, n, nxt), 'amt_domain_sumflux_state')
+    if (n /= nsmall .or. nxt /= 1 .or. .not. c_associated(amt_domain_sumflux_ptr(d, 2_c_int))) error stop 6
+    ! the caller's arrays: the same loop accumulated by hand, then by the pointer-level call on the handle's stream
+    call amt_check(amt_domain_set_sumflux(d, int(nsmall, c_int), amt_domain_field_ptr(outs, acc(1)),                     &
+                   amt_domain_field_ptr(outs, acc(2)), amt_domain_field_ptr(outs, acc(3))), 'amt_domain_set_sumflux')
+    do it = 1, int(nsmall, c_int)
+       call amt_check(amt_domain_sumflux_accumulate(d), 'amt_domain_sumflux_accumulate')
+    end do
+    call amt_check(amt_domain_set_sumflux(d, 0_c_int, c_null_ptr, c_null_ptr, c_null_ptr), 'amt_domain_set_sumflux')
+    stream = amt_domain_stream(d)
+    do it = 1, int(nsmall, c_int)
+       call sumflux_device(stream, 1_c_int, it, amt_domain_field_ptr(outs, acc(1)), amt_domain_field_ptr(outs, acc(2)),    &
+                           amt_domain_field_ptr(outs, acc(3)), d, .false.)
+    end do
+    call amt_check(amt_domain_sync(d), 'amt_domain_sync')
+    print '(a,i0,a)', 'flux averages over ', nsmall, ' sub-steps on the device (ru_m, rv_m, ww_m)'
+    do k = 1, 3
+       call amt_check(amt_domain_download(outs, acc(k), c_loc(o3)), 'amt_domain_download')
+       print '(a,a,a,es24.16)', 'checksum of ', aname(k), ' over the tile: ', sum(real(o3(its:ite, kts:kte, jts:jte), 8))
+       if (len_trim(outdir) > 0) call dump3(aname(k), o3)
+    end do
+    call amt_check(amt_domain_destroy(d), 'amt_domain_destroy')
+    call amt_check(amt_domain_destroy(outs), 'amt_domain_destroy')
+    ! an ensemble: every member's accumulation in one launch
+    call amt_check(amt_ensemble_create(e, mm, wb, px, sp, ne, ids, ide, jds, jde, kde,                                     &
+                                       ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte), 'amt_ensemble_create')
+    call amt_check(amt_ensemble_set_scalars(e, real(rdx, c_double), real(rdy, c_double), real(dts, c_double),            &
+                                            real(epssm, c_double)), 'amt_ensemble_set_scalars')
+    call amt_check(amt_ensemble_fill_synthetic(e, seed, int(ims, c_long), int(kms-1, c_long), int(jms, c_long),          &
+                   int(ni+2, c_long), int(nk+1, c_long), int(nj+2, c_long)), 'amt_ensemble_fill_synthetic')
+    call amt_check(amt_ensemble_set_sumflux(e, int(nsmall, c_int), c_null_ptr, c_null_ptr, c_null_ptr), 'amt_ensemble_set_sumflux')
+    call amt_check(amt_ensemble_step(e, int(nsmall, c_int)), 'amt_ensemble_step')
+    call amt_check(amt_ensemble_sumflux_accumulate(e), 'amt_ensemble_sumflux_accumulate')      ! iteration 1 of the next loop
+    call amt_check(amt_ensemble_sumflux_state(e, n, nxt), 'amt_ensemble_sumflux_state')
+    if (n /= nsmall .or. nxt /= merge(1, 2, nsmall == 1)) error stop 7
+    ! pointer level on the member-stacked arrays, into the library's accumulators: iteration 1 once more (acc is not read)
+    call sumflux_device(amt_ensemble_stream(e), mm, 1_c_int, amt_ensemble_sumflux_ptr(e, 0_c_int),                          &
+                        amt_ensemble_sumflux_ptr(e, 1_c_int), amt_ensemble_sumflux_ptr(e, 2_c_int), e, .true.)
+    call amt_check(amt_ensemble_sync(e), 'amt_ensemble_sync')
+    print '(a,i0,a)', 'flux averages of an ensemble of ', mm, ' members: one launch per sub-step'
+    call amt_check(amt_ensemble_destroy(e), 'amt_ensemble_destroy')
+  end subroutine
+
+  subroutine sumflux_device(stream, mm, it, ru_m, rv_m, ww_m, h, is_ensemble)
+    type(c_ptr), intent(in) :: stream, ru_m, rv_m, ww_m, h
+    integer(c_int), intent(in) :: mm, it
+    logical, intent(in) :: is_ensemble
+    type(c_ptr) :: p(0:25)
+    integer(c_int) :: f
+    do f = 0, 25
+       if (is_ensemble) then
+          p(f) = amt_ensemble_field_ptr(h, f)
+       else
+          p(f) = amt_domain_field_ptr(h, f)
+       end if
+    end do
+    if (storage_size(rdx) == 64) then
+       rc = amt_sumflux_device_f64(stream, mm, ru_m, rv_m, ww_m, p(AMT_F_U), p(AMT_F_V), p(AMT_F_WW), p(AMT_F_U_1),        &
+                                   p(AMT_F_V_1), p(AMT_F_WW_1), p(AMT_F_MUU), p(AMT_F_MUV), p(AMT_F_MSFUY),               &
+                                   p(AMT_F_MSFVX_INV), it, int(nsmall, c_int),                                            &
+                                   ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte)
+    else
+       rc = amt_sumflux_device_f32(stream, mm, ru_m, rv_m, ww_m, p(AMT_F_U), p(AMT_F_V), p(AMT_F_WW), p(AMT_F_U_1),        &
+                                   p(AMT_F_V_1), p(AMT_F_WW_1), p(AMT_F_MUU), p(AMT_F_MUV), p(AMT_F_MSFUY),               &
+                                   p(AMT_F_MSFVX_INV), it, int(nsmall, c_int),                                            &
+                                   ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte)
+    end if
+    call amt_check(rc, 'amt_sumflux_device')
+  end subroutine
 
   ! An ensemble of `members` members of this shape, stepped nsweeps times, and what a host asks of it at an output time: the
   ! mean, the sample variance and the envelope over the members, computed where the members live.  The outputs are arrays of

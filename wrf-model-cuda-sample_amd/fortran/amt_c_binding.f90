@@ -1016,6 +1016,86 @@ MODULE amt_c_binding
          type(c_ptr), value :: mean, var, lo, hi
          integer(c_int) :: rc
       end function
+      ! (14) the acoustic loop's flux averages ru_m, rv_m, ww_m (WRF's sumflux): sub-step `iteration` of n_small_steps adds u, v,
+      ! ww into the accumulators, the last one turns the sums into the averages.  Pointer level (members = 1 for a single
+      ! patch): every array is a DEVICE pointer; asynchronous on hip_stream
+      function amt_sumflux_device_f32(hip_stream, members, ru_m, rv_m, ww_m, u, v, ww, u_1, v_1, ww_1,                      &
+                                      muu, muv, msfuy, msfvx_inv, iteration, n_small_steps,                              &
+                                      ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,                            &
+                                      its, ite, jts, jte, kts, kte) bind(C, name="amt_sumflux_device_f32") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: hip_stream
+         integer(c_int), value :: members
+         type(c_ptr), value :: ru_m, rv_m, ww_m, u, v, ww, u_1, v_1, ww_1, muu, muv, msfuy, msfvx_inv   ! device pointers
+         integer(c_int), value :: iteration, n_small_steps
+         integer(c_int), value :: ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme
+         integer(c_int), value :: its, ite, jts, jte, kts, kte
+         integer(c_int) :: rc
+      end function
+      function amt_sumflux_device_f64(hip_stream, members, ru_m, rv_m, ww_m, u, v, ww, u_1, v_1, ww_1,                      &
+                                      muu, muv, msfuy, msfvx_inv, iteration, n_small_steps,                              &
+                                      ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,                            &
+                                      its, ite, jts, jte, kts, kte) bind(C, name="amt_sumflux_device_f64") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: hip_stream
+         integer(c_int), value :: members
+         type(c_ptr), value :: ru_m, rv_m, ww_m, u, v, ww, u_1, v_1, ww_1, muu, muv, msfuy, msfvx_inv   ! device pointers
+         integer(c_int), value :: iteration, n_small_steps
+         integer(c_int), value :: ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme
+         integer(c_int), value :: its, ite, jts, jte, kts, kte
+         integer(c_int) :: rc
+      end function
+      ! set: n_small_steps = 0 off (the default); >= 1 with three c_null_ptr: the library allocates the accumulators, with
+      ! three device pointers: the caller's.  Every sweep of the handle's stepping (amt_domain_step, amt_slab_step,
+      ! amt_grid_step, amt_*_step_end ...) is then followed by one accumulation; the iteration counter runs 1..n and wraps
+      function amt_domain_set_sumflux(handle, n_small_steps, ru_m, rv_m, ww_m) bind(C, name="amt_domain_set_sumflux") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: n_small_steps
+         type(c_ptr), value :: ru_m, rv_m, ww_m
+         integer(c_int) :: rc
+      end function
+      function amt_domain_sumflux_accumulate(handle) bind(C, name="amt_domain_sumflux_accumulate") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int) :: rc
+      end function
+      function amt_domain_sumflux_state(handle, n, next_iteration) bind(C, name="amt_domain_sumflux_state") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), intent(out) :: n, next_iteration
+         integer(c_int) :: rc
+      end function
+      function amt_domain_sumflux_ptr(handle, which) bind(C, name="amt_domain_sumflux_ptr") result(ptr)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: which                                              ! 0 ru_m, 1 rv_m, 2 ww_m
+         type(c_ptr) :: ptr
+      end function
+      function amt_ensemble_set_sumflux(handle, n_small_steps, ru_m, rv_m, ww_m) bind(C, name="amt_ensemble_set_sumflux") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: n_small_steps
+         type(c_ptr), value :: ru_m, rv_m, ww_m
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_sumflux_accumulate(handle) bind(C, name="amt_ensemble_sumflux_accumulate") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_sumflux_state(handle, n, next_iteration) bind(C, name="amt_ensemble_sumflux_state") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), intent(out) :: n, next_iteration
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_sumflux_ptr(handle, which) bind(C, name="amt_ensemble_sumflux_ptr") result(ptr)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: which
+         type(c_ptr) :: ptr
+      end function
    end interface
 
    ! enum amt_field (include/amt_synth.h): the Fortran argument order

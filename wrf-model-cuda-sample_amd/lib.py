@@ -202,6 +202,16 @@ SYMBOLS = {
     "amt_moments_device_f32": (_I, [_P, _P, _I, _I] + [_I] * 12 + [_P] * 4),
     "amt_moments_device_f64": (_I, [_P, _P, _I, _I] + [_I] * 12 + [_P] * 4),
     "amt_ensemble_moments": (_I, [_P, _I, _I] + [_P] * 4),
+    "amt_sumflux_device_f32": (_I, [_P, _I] + [_P] * 13 + [_I] * (2 + 17)),
+    "amt_sumflux_device_f64": (_I, [_P, _I] + [_P] * 13 + [_I] * (2 + 17)),
+    "amt_domain_set_sumflux": (_I, [_P, _I, _P, _P, _P]),
+    "amt_domain_sumflux_accumulate": (_I, [_P]),
+    "amt_domain_sumflux_state": (_I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "amt_domain_sumflux_ptr": (_P, [_P, _I]),
+    "amt_ensemble_set_sumflux": (_I, [_P, _I, _P, _P, _P]),
+    "amt_ensemble_sumflux_accumulate": (_I, [_P]),
+    "amt_ensemble_sumflux_state": (_I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "amt_ensemble_sumflux_ptr": (_P, [_P, _I]),
     "amt_halo_plan": (_I, [_I] * (4 + 17 + 5) + [ctypes.POINTER(HaloMessage), _I, ctypes.POINTER(_I)]),
     "amt_grid_halo_messages": (_I, [_P, ctypes.POINTER(HaloMessage), _I, ctypes.POINTER(_I)]),
     "amt_slab_halo_messages": (_I, [_P, ctypes.POINTER(HaloMessage), _I, ctypes.POINTER(_I)]),
@@ -295,3 +305,25 @@ class HandleDiag:
         out = GuardReport()
         check(self._fn("guard_report")(self.handle, ctypes.byref(out)))
         return out
+
+    # the acoustic loop's flux averages ru_m, rv_m, ww_m (header section 14)
+    def set_sumflux(self, n_small_steps: int, ru_m=None, rv_m=None, ww_m=None) -> None:
+        """``set_sumflux``: 0 = off.  n >= 1: every sweep of the handle's stepping is followed by one accumulation, the counter
+        running 1..n and wrapping.  Without arrays the library allocates the accumulators; otherwise all three are device
+        tensors (or addresses) of one 3-D field's extents (times the members), which the caller keeps alive."""
+        ptr = lambda a: ctypes.c_void_p(None if a is None else a.data_ptr() if hasattr(a, "data_ptr") else int(a))
+        check(self._fn("set_sumflux")(self.handle, int(n_small_steps), ptr(ru_m), ptr(rv_m), ptr(ww_m)))
+
+    def sumflux_accumulate(self) -> None:
+        """One accumulation now, asynchronous on the handle's stream; advances the counter."""
+        check(self._fn("sumflux_accumulate")(self.handle))
+
+    def sumflux_state(self):
+        """(n_small_steps, next_iteration); n_small_steps = 0: off."""
+        n, nxt = ctypes.c_int(), ctypes.c_int()
+        check(self._fn("sumflux_state")(self.handle, ctypes.byref(n), ctypes.byref(nxt)))
+        return int(n.value), int(nxt.value)
+
+    def sumflux_ptr(self, which: int) -> int:
+        """Device address of ru_m (0), rv_m (1) or ww_m (2); 0 while the setting is off."""
+        return int(self._fn("sumflux_ptr")(self.handle, int(which)) or 0)

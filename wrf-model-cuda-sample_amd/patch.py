@@ -394,7 +394,37 @@ def _substep_inputs(stepper, dom, seed, sweep, sides):
             stepper._lib.check(stepper.L.amt_domain_poison_halos(dom, sides))
 
 
-class NativeSlabStepper:
+class _SumfluxOfStepper:
+    """``sumflux=n`` of the native steppers (header section 14): every sweep is followed by one accumulation of this rank's own
+    tile into ru_m, rv_m, ww_m, which the library allocates; the counter runs 1..n and wraps.  Nothing is exchanged for it."""
+
+    def sumflux_state(self):
+        """(n_small_steps, next_iteration); n_small_steps = 0: off."""
+        n, nxt = self._ct.c_int(), self._ct.c_int()
+        self._lib.check(self.L.amt_domain_sumflux_state(self._dom, self._ct.byref(n), self._ct.byref(nxt)))
+        return int(n.value), int(nxt.value)
+
+    def sumflux_arrays(self):
+        """ru_m, rv_m, ww_m as torch tensors that view the library's device arrays (valid while the stepper lives)."""
+        import torch
+        b, t0 = self.patch.bounds, self.patch.arrays["t_1"]
+        out = []
+        for which in range(3):
+            ptr = self.L.amt_domain_sumflux_ptr(self._dom, which)
+            if not ptr:
+                raise self._lib.AmtError(self._lib.ERR_INVALID_ARG, "the flux averages are off")
+
+            class _View:
+                pass
+            v = _View()
+            v.owner = self
+            v.__cuda_array_interface__ = {"shape": tuple(b.shape("ww")), "typestr": "<f8" if t0.element_size() == 8 else "<f4",
+                                          "data": (int(ptr), False), "version": 2, "strides": None}
+            out.append(torch.as_tensor(v, device=t0.device))
+        return tuple(out)
+
+
+class NativeSlabStepper(_SumfluxOfStepper):
     """The same j-slab sweep as ``SlabStepper`` driven by the C++ runtime behind the C-ABI
     (``amt_slab_*``, include/amt_advance_mu_t.h section 5): ``ncclSend/ncclRecv`` of the halo rows
     in one RCCL group on a communication stream, the two edge rows behind them on that stream, the
@@ -415,7 +445,7 @@ class NativeSlabStepper:
 
     def __init__(self, patch: Patch, rank: int, world: int, unique_id: Optional[bytes] = None, *,
                  stream=None, overlap: bool = True, variant: int = 0, loopback: bool = False, transport: str = "rccl",
-                 cyclic=(False, False), spec_bdy: bool = False):
+                 cyclic=(False, False), spec_bdy: bool = False, sumflux: int = 0):
         import ctypes
         import torch
         from . import lib as _lib
@@ -447,6 +477,8 @@ class NativeSlabStepper:
                 _lib.check(L.amt_domain_set_variant(self._dom, int(variant)))
                 if spec_bdy:                                  # the boundary-zone update behind every sweep (header section 12)
                     _lib.check(L.amt_domain_set_spec_bdy(self._dom, 1))
+                if sumflux:                                   # the flux averages behind every sweep (header section 14)
+                    _lib.check(L.amt_domain_set_sumflux(self._dom, int(sumflux), None, None, None))
                 if transport not in ("rccl", "ipc"):
                     raise ValueError("transport is 'rccl' or 'ipc'")
                 flags = ((0 if overlap else self.NO_OVERLAP) | (self.LOOPBACK if loopback else 0)
@@ -530,7 +562,7 @@ class NativeSlabStepper:
             pass
 
 
-class NativeGridStepper:
+class NativeGridStepper(_SumfluxOfStepper):
     """advance_mu_t on patch (ri, rj) of pi x pj driven by the C++ runtime behind the C-ABI (``amt_grid_*``, header section 5b):
     HIP pack / unpack kernels for the strided halo columns, rows and packed columns in ONE exchange (RCCL group or IPC
     pulls), interior cells on the patch's stream beside it, boundary rows and columns behind it on the communication stream.
@@ -541,7 +573,7 @@ class NativeGridStepper:
 
     def __init__(self, patch: Patch, ri: int, rj: int, pi: int, pj: int, unique_id: Optional[bytes] = None, *,
                  stream=None, overlap: bool = True, variant: int = 0, loopback: bool = False, transport: str = "rccl",
-                 cyclic=(False, False), spec_bdy: bool = False):
+                 cyclic=(False, False), spec_bdy: bool = False, sumflux: int = 0):
         import ctypes
         import torch
         from . import lib as _lib
@@ -573,6 +605,8 @@ class NativeGridStepper:
                 _lib.check(L.amt_domain_set_variant(self._dom, int(variant)))
                 if spec_bdy:                                  # the boundary-zone update behind every sweep (header section 12)
                     _lib.check(L.amt_domain_set_spec_bdy(self._dom, 1))
+                if sumflux:                                   # the flux averages behind every sweep (header section 14)
+                    _lib.check(L.amt_domain_set_sumflux(self._dom, int(sumflux), None, None, None))
                 flags = ((0 if overlap else self.NO_OVERLAP) | (self.LOOPBACK if loopback else 0)
                          | (self.TRANSPORT_IPC if transport == "ipc" else 0)
                          | (CYCLIC_X_FLAG if self.cyclic[0] else 0) | (CYCLIC_Y_FLAG if self.cyclic[1] else 0))
@@ -699,7 +733,7 @@ class HaloMessageView:
         self.side, self.peer, self.send, self.recv, self.on_host = side, peer, send, recv, on_host
 
 
-class ExternalGridStepper:
+class ExternalGridStepper(_SumfluxOfStepper):
     """advance_mu_t on patch (ri, rj) of pi x pj with the HOST as the transport (``AMT_SLAB_TRANSPORT_EXTERNAL``): per sweep
     ``begin()`` (pack + interior), ``halo_wait()``, the host copies every ``send`` into the matching ``recv`` of the peer (an
     MPI host: Isend / Irecv with tag = side), ``end()`` (unpack + boundary cells).  Creation is not collective and needs no
@@ -710,7 +744,7 @@ class ExternalGridStepper:
     _HANDLE, _SLAB = "amt_grid", False
 
     def __init__(self, patch: Patch, ri: int, rj: int, pi: int, pj: int, *, cyclic=(False, False), overlap: bool = True,
-                 host_buffers: bool = False, stream=None, variant: int = 0, spec_bdy: bool = False):
+                 host_buffers: bool = False, stream=None, variant: int = 0, spec_bdy: bool = False, sumflux: int = 0):
         import ctypes
         import torch
         from . import lib as _lib
@@ -743,6 +777,8 @@ class ExternalGridStepper:
                 _lib.check(L.amt_domain_set_variant(self._dom, int(variant)))
                 if spec_bdy:                                  # the boundary-zone update behind every sweep (header section 12)
                     _lib.check(L.amt_domain_set_spec_bdy(self._dom, 1))
+                if sumflux:                                   # the flux averages behind every sweep (header section 14)
+                    _lib.check(L.amt_domain_set_sumflux(self._dom, int(sumflux), None, None, None))
                 self.flags = (EXTERNAL_FLAG | (0 if overlap else 1) | (HOST_BUFFERS_FLAG if host_buffers else 0)
                               | (CYCLIC_X_FLAG if self.cyclic[0] else 0) | (CYCLIC_Y_FLAG if self.cyclic[1] else 0))
                 if self._SLAB:
