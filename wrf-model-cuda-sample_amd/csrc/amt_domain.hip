@@ -6,9 +6,17 @@
 #include <time.h>
 #include <unistd.h>
 
-extern "C" int amt_domain_destroy(amt_domain *d)
+void amt_domain_set_shape(amt_domain *d, AMT_SHAPE_SIG)
 {
-    if (!d) return AMT_OK;
+    d->dtype_bytes = dtype_bytes;
+    d->periodic_x = periodic_x; d->specified = specified; d->nested = nested;
+    d->ids = ids; d->ide = ide; d->jds = jds; d->jde = jde; d->kde = kde;
+    d->ims = ims; d->ime = ime; d->jms = jms; d->jme = jme; d->kms = kms; d->kme = kme;
+    d->its = its; d->ite = ite; d->jts = jts; d->jte = jte; d->kts = kts; d->kte = kte;
+}
+
+void amt_handle_close(amt_domain *d)
+{
     DeviceScope scope(d->device);
     amt_diag_release(d);
     amt_sumflux_release(d);
@@ -18,37 +26,15 @@ extern "C" int amt_domain_destroy(amt_domain *d)
     if (d->ev0) (void)hipEventDestroy(d->ev0);
     if (d->ev1) (void)hipEventDestroy(d->ev1);
     if (d->stream && d->owns_stream) (void)hipStreamDestroy(d->stream);
-    delete d;
-    return AMT_OK;
 }
 
-// fields == nullptr: allocate the 26 arrays (amt_domain_create).  Otherwise adopt the caller's
-// device arrays and, when given, the caller's stream (amt_domain_wrap): nothing is copied and
-// nothing of the caller's is freed by amt_domain_destroy.
-static int amt_domain_make(amt_domain **out, int dtype_bytes,
-                           int periodic_x, int specified, int nested,
-                           int ids, int ide, int jds, int jde, int kde,
-                           int ims, int ime, int jms, int jme, int kms, int kme,
-                           int its, int ite, int jts, int jte, int kts, int kte,
-                           void *const *fields, void *hip_stream)
+// fields == nullptr: allocate the 26 arrays, `members` of every rank-3 and rank-2 one (create).  Otherwise adopt the caller's
+// device arrays and, when given, the caller's stream (wrap): nothing is copied and nothing of the caller's is freed by close.
+int amt_handle_open(const char *who, amt_domain *d, int members, void *const *fields, void *hip_stream)
 {
-    if (!out) return amt_fail(AMT_ERR_INVALID_ARG, "null out pointer");
-    *out = nullptr;
-    if (dtype_bytes != 4 && dtype_bytes != 8) return amt_fail(AMT_ERR_INVALID_ARG, "dtype_bytes must be 4 or 8");
-    if (ime < ims || jme < jms || kme < kms) return amt_fail(AMT_ERR_PRECONDITION, "empty memory extents");
-    if (fields)
-        for (int f = 0; f < AMT_F_COUNT; ++f)
-            if (!fields[f]) return amt_fail(AMT_ERR_INVALID_ARG, "amt_domain_wrap: field %d is a null pointer", f);
     int ndev = 0;
     AMT_HIP(hipGetDeviceCount(&ndev));
     if (ndev < 1) return amt_fail(AMT_ERR_NO_DEVICE, "no HIP device visible");
-    amt_domain *d = new (std::nothrow) amt_domain;
-    if (!d) return amt_fail(AMT_ERR_ALLOC, "host allocation failed");
-    d->dtype_bytes = dtype_bytes;
-    d->periodic_x = periodic_x; d->specified = specified; d->nested = nested;
-    d->ids = ids; d->ide = ide; d->jds = jds; d->jde = jde; d->kde = kde;
-    d->ims = ims; d->ime = ime; d->jms = jms; d->jme = jme; d->kms = kms; d->kme = kme;
-    d->its = its; d->ite = ite; d->jts = jts; d->jte = jte; d->kts = kts; d->kte = kte;
     d->owns_fields = (fields == nullptr);
     d->owns_stream = (hip_stream == nullptr);
     hipError_t e = hipGetDevice(&d->device);
@@ -58,15 +44,36 @@ static int amt_domain_make(amt_domain **out, int dtype_bytes,
     if (e == hipSuccess) e = hipEventCreate(&d->ev1);
     for (int f = 0; f < AMT_F_COUNT && e == hipSuccess; ++f) {
         if (fields) d->field[f] = fields[f];
-        else e = hipMalloc(&d->field[f], d->count(f) * (size_t)dtype_bytes);
+        else e = hipMalloc(&d->field[f], d->count(f) * (amt_field_rank(f) == 1 ? 1 : (size_t)members) * (size_t)d->dtype_bytes);
     }
-    if (e != hipSuccess) {
-        amt_domain_destroy(d);
-        return amt_fail(e == hipErrorOutOfMemory ? AMT_ERR_ALLOC : AMT_ERR_HIP,
-                        "amt_domain_create: %s", hipGetErrorString(e));
-    }
-    *out = d;
+    if (e == hipSuccess) return AMT_OK;
+    amt_handle_close(d);
+    return amt_fail(e == hipErrorOutOfMemory ? AMT_ERR_ALLOC : AMT_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+}
+
+extern "C" int amt_domain_destroy(amt_domain *d)
+{
+    if (d) amt_handle_close(d);
+    delete d;
     return AMT_OK;
+}
+
+static int amt_domain_make(amt_domain **out, AMT_SHAPE_SIG, void *const *fields, void *hip_stream)
+{
+    if (!out) return amt_fail(AMT_ERR_INVALID_ARG, "null out pointer");
+    *out = nullptr;
+    if (dtype_bytes != 4 && dtype_bytes != 8) return amt_fail(AMT_ERR_INVALID_ARG, "dtype_bytes must be 4 or 8");
+    if (ime < ims || jme < jms || kme < kms) return amt_fail(AMT_ERR_PRECONDITION, "empty memory extents");
+    if (fields)
+        for (int f = 0; f < AMT_F_COUNT; ++f)
+            if (!fields[f]) return amt_fail(AMT_ERR_INVALID_ARG, "amt_domain_wrap: field %d is a null pointer", f);
+    amt_domain *d = new (std::nothrow) amt_domain;
+    if (!d) return amt_fail(AMT_ERR_ALLOC, "host allocation failed");
+    amt_domain_set_shape(d, AMT_SHAPE_ARGS);
+    const int rc = amt_handle_open("amt_domain_create", d, 1, fields, hip_stream);
+    if (rc) delete d;
+    else *out = d;
+    return rc;
 }
 
 static int amt_domain_tune(amt_domain *d, int tries, float *ms_per_try, bool preserve);
@@ -102,14 +109,9 @@ static int amt_placement_lock(int device)
     return fd;
 }
 
-extern "C" int amt_domain_create(amt_domain **out, int dtype_bytes,
-                                 int periodic_x, int specified, int nested,
-                                 int ids, int ide, int jds, int jde, int kde,
-                                 int ims, int ime, int jms, int jme, int kms, int kme,
-                                 int its, int ite, int jts, int jte, int kts, int kte)
+extern "C" int amt_domain_create(amt_domain **out, AMT_SHAPE_SIG)
 {
-    int rc = amt_domain_make(out, dtype_bytes, periodic_x, specified, nested, ids, ide, jds, jde, kde,
-                             ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte, nullptr, nullptr);
+    int rc = amt_domain_make(out, AMT_SHAPE_ARGS, nullptr, nullptr);
     if (rc != AMT_OK) return rc;
     // Placement sampling, on by default (a host that creates its handle ONCE must get the sweep time the
     // bench prints).  Which physical pages the driver hands out moves a sweep of a large domain by +-3 % and cannot be steered
@@ -146,50 +148,74 @@ extern "C" int amt_domain_create(amt_domain **out, int dtype_bytes,
     return AMT_OK;
 }
 
-extern "C" int amt_domain_wrap(amt_domain **out, int dtype_bytes,
-                               int periodic_x, int specified, int nested,
-                               int ids, int ide, int jds, int jde, int kde,
-                               int ims, int ime, int jms, int jme, int kms, int kme,
-                               int its, int ite, int jts, int jte, int kts, int kte,
-                               void *const *fields, void *hip_stream)
+extern "C" int amt_domain_wrap(amt_domain **out, AMT_SHAPE_SIG, void *const *fields, void *hip_stream)
 {
     if (!fields) return amt_fail(AMT_ERR_INVALID_ARG, "amt_domain_wrap needs the %d device pointers", (int)AMT_F_COUNT);
-    return amt_domain_make(out, dtype_bytes, periodic_x, specified, nested, ids, ide, jds, jde, kde,
-                           ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte, fields, hip_stream);
+    return amt_domain_make(out, AMT_SHAPE_ARGS, fields, hip_stream);
 }
 
-extern "C" int amt_domain_set_scalars(amt_domain *d, double rdx, double rdy, double dts, double epssm)
+int amt_handle_set_scalars(amt_domain *d, double rdx, double rdy, double dts, double epssm)
 {
-    if (!d) return amt_fail(AMT_ERR_INVALID_ARG, "null domain");
     d->rdx = rdx; d->rdy = rdy; d->dts = dts; d->epssm = epssm;
     return AMT_OK;
 }
 
-extern "C" int amt_domain_set_variant(amt_domain *d, int variant)
+int amt_handle_set_variant(amt_domain *d, int variant)
 {
-    if (!d) return amt_fail(AMT_ERR_INVALID_ARG, "null domain");
     if (variant < AMT_VARIANT_AUTO || variant > AMT_VARIANT_MARCH)
         return amt_fail(AMT_ERR_INVALID_ARG, "unknown variant %d", variant);
     d->variant = variant;
     return AMT_OK;
 }
 
+int amt_handle_copy(amt_domain *d, void *dev, void *host, size_t bytes, bool up)
+{
+    DeviceScope scope(d->device);
+    if (up) AMT_HIP(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, d->stream));
+    else AMT_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, d->stream));
+    AMT_HIP(hipStreamSynchronize(d->stream));
+    return AMT_OK;
+}
+
+int amt_handle_fill(amt_domain *d, int members, uint64_t field_mask, uint64_t seed,
+                    long gi0, long gk0, long gj0, long gidim, long gkdim, long gjdim)
+{
+    DeviceScope scope(d->device);
+    const long idim = d->ime - d->ims + 1, kdim = d->kme - d->kms + 1, jdim = d->jme - d->jms + 1;
+    for (int f = 0; f < AMT_F_COUNT; ++f) {
+        if (!(field_mask & AMT_FIELD_BIT(f))) continue;
+        const size_t bytes = d->count(f) * (size_t)d->dtype_bytes;
+        for (int m = 0; m < (amt_field_rank(f) == 1 ? 1 : members); ++m) {       // the vertical metrics do not depend on the seed
+            int rc = amt_synth_fill_device(d->stream, f, d->dtype_bytes, static_cast<char *>(d->field[f]) + (size_t)m * bytes,
+                                           seed + (uint64_t)m, idim, kdim, jdim, gi0, gk0, gj0, gidim, gkdim, gjdim);
+            if (rc) return rc;
+        }
+    }
+    return AMT_OK;
+}
+
+static int amt_null_domain() { return amt_fail(AMT_ERR_INVALID_ARG, "null domain"); }
+
+extern "C" int amt_domain_set_scalars(amt_domain *d, double rdx, double rdy, double dts, double epssm)
+{
+    return d ? amt_handle_set_scalars(d, rdx, rdy, dts, epssm) : amt_null_domain();
+}
+
+extern "C" int amt_domain_set_variant(amt_domain *d, int variant)
+{
+    return d ? amt_handle_set_variant(d, variant) : amt_null_domain();
+}
+
 extern "C" int amt_domain_upload(amt_domain *d, int field, const void *host)
 {
     if (!d || !host || field < 0 || field >= AMT_F_COUNT) return amt_fail(AMT_ERR_INVALID_ARG, "bad upload argument");
-    DeviceScope scope(d->device);
-    AMT_HIP(hipMemcpyAsync(d->field[field], host, d->count(field) * d->dtype_bytes, hipMemcpyHostToDevice, d->stream));
-    AMT_HIP(hipStreamSynchronize(d->stream));
-    return AMT_OK;
+    return amt_handle_copy(d, d->field[field], const_cast<void *>(host), d->count(field) * d->dtype_bytes, true);
 }
 
 extern "C" int amt_domain_download(amt_domain *d, int field, void *host)
 {
     if (!d || !host || field < 0 || field >= AMT_F_COUNT) return amt_fail(AMT_ERR_INVALID_ARG, "bad download argument");
-    DeviceScope scope(d->device);
-    AMT_HIP(hipMemcpyAsync(host, d->field[field], d->count(field) * d->dtype_bytes, hipMemcpyDeviceToHost, d->stream));
-    AMT_HIP(hipStreamSynchronize(d->stream));
-    return AMT_OK;
+    return amt_handle_copy(d, d->field[field], host, d->count(field) * d->dtype_bytes, false);
 }
 
 // rows j_lo..j_hi (Fortran indices, inside jms:jme) of a rank-3 or rank-2 field: contiguous in the
@@ -204,12 +230,7 @@ static int amt_domain_copy_rows(amt_domain *d, int field, int j_lo, int j_hi, vo
     const size_t idim = d->ime - d->ims + 1, kdim = d->kme - d->kms + 1;
     const size_t row = (rank == 3 ? idim * kdim : idim) * (size_t)d->dtype_bytes;
     char *dev = static_cast<char *>(d->field[field]) + (size_t)(j_lo - d->jms) * row;
-    const size_t bytes = (size_t)(j_hi - j_lo + 1) * row;
-    DeviceScope scope(d->device);
-    if (up) AMT_HIP(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, d->stream));
-    else AMT_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, d->stream));
-    AMT_HIP(hipStreamSynchronize(d->stream));
-    return AMT_OK;
+    return amt_handle_copy(d, dev, host, (size_t)(j_hi - j_lo + 1) * row, up);
 }
 
 extern "C" int amt_domain_upload_rows(amt_domain *d, int field, int j_lo, int j_hi, const void *host)
@@ -223,35 +244,17 @@ extern "C" int amt_domain_download_rows(amt_domain *d, int field, int j_lo, int 
 }
 
 extern "C" int amt_domain_fill_synthetic(amt_domain *d, uint64_t seed,
-                                         long gi0, long gk0, long gj0,
-                                         long gidim, long gkdim, long gjdim)
+                                         long gi0, long gk0, long gj0, long gidim, long gkdim, long gjdim)
 {
-    if (!d) return amt_fail(AMT_ERR_INVALID_ARG, "null domain");
-    DeviceScope scope(d->device);
-    const long idim = d->ime - d->ims + 1, kdim = d->kme - d->kms + 1, jdim = d->jme - d->jms + 1;
-    for (int f = 0; f < AMT_F_COUNT; ++f) {
-        int rc = amt_synth_fill_device(d->stream, f, d->dtype_bytes, d->field[f], seed,
-                                       idim, kdim, jdim, gi0, gk0, gj0, gidim, gkdim, gjdim);
-        if (rc) return rc;
-    }
-    return AMT_OK;
+    return d ? amt_handle_fill(d, 1, ~0ull, seed, gi0, gk0, gj0, gidim, gkdim, gjdim) : amt_null_domain();
 }
 
 extern "C" int amt_domain_fill_fields(amt_domain *d, uint64_t field_mask, uint64_t seed,
-                                      long gi0, long gk0, long gj0,
-                                      long gidim, long gkdim, long gjdim)
+                                      long gi0, long gk0, long gj0, long gidim, long gkdim, long gjdim)
 {
-    if (!d) return amt_fail(AMT_ERR_INVALID_ARG, "null domain");
+    if (!d) return amt_null_domain();
     if (field_mask >> AMT_F_COUNT) return amt_fail(AMT_ERR_INVALID_ARG, "field mask names a field beyond AMT_F_COUNT");
-    DeviceScope scope(d->device);
-    const long idim = d->ime - d->ims + 1, kdim = d->kme - d->kms + 1, jdim = d->jme - d->jms + 1;
-    for (int f = 0; f < AMT_F_COUNT; ++f) {
-        if (!(field_mask & AMT_FIELD_BIT(f))) continue;
-        int rc = amt_synth_fill_device(d->stream, f, d->dtype_bytes, d->field[f], seed,
-                                       idim, kdim, jdim, gi0, gk0, gj0, gidim, gkdim, gjdim);
-        if (rc) return rc;
-    }
-    return AMT_OK;
+    return amt_handle_fill(d, 1, field_mask, seed, gi0, gk0, gj0, gidim, gkdim, gjdim);
 }
 
 // NaN into up to twelve strided runs in one launch: job q = `count` elements from `base` at stride `stride` (a row of the
@@ -315,82 +318,139 @@ extern "C" int amt_domain_poison_halos(amt_domain *d, int sides)
                                : amt_domain_poison_t<uint32_t>(d, sides, 0x7fc00000u);
 }
 
+// ---------------------------------------------------------------------------
+// The sweep sequence of a resident handle (amt_internal.h): what amt_domain_step and amt_ensemble_step enqueue.
+// ---------------------------------------------------------------------------
+int amt_handle_behind_sweep(const char *who, amt_domain *d, int members)
+{
+    // specified / nested boundaries: the boundary zone is advanced behind the sweep, where WRF has its spec_bdyupdate calls
+    const int rc = d->spec_bdy ? amt_bdy_update_domain(who, d, members) : AMT_OK;
+    // the acoustic loop's flux averages: one accumulation behind the boundary-zone update, where WRF has its sumflux call
+    return rc == AMT_OK && d->sumflux_n ? amt_sumflux_accumulate_domain(who, d, members) : rc;
+}
+
+namespace {
 template <typename T>
-static int amt_domain_step_t(amt_domain *d, int n_sweeps)
+int handle_step_t(const char *who, amt_domain *d, int members, bool stacked, int n_sweeps)
 {
     AmtArgs<T> a;
     amt_domain_args<T>(d, a);
     // an armed guard that already shows a finding: nothing is enqueued (no wait: the record is in host memory)
-    if (d->guard_every) { const int rc = amt_diag_guard_status("amt_domain_step", d); if (rc) return rc; }
+    if (d->guard_every) { const int rc = amt_diag_guard_status(who, d); if (rc) return rc; }
     for (int s = 0; s < n_sweeps; ++s) {
         // cyclic boundaries: the wrap cells are refreshed in front of every sweep, on the same stream (the inputs are final there)
-        int rc = d->cyclic ? amt_cyclic_refresh_domain("amt_domain_step", d, d->cyclic, 1) : AMT_OK;
-        if (rc == AMT_OK) rc = amt_device_call<T>(d->stream, d->variant, a);
-        // specified / nested boundaries: the boundary zone is advanced behind the sweep, where WRF has its spec_bdyupdate calls
-        if (rc == AMT_OK && d->spec_bdy) rc = amt_bdy_update_domain("amt_domain_step", d, 1);
-        // the acoustic loop's flux averages: one accumulation behind the boundary-zone update, where WRF has its sumflux call
-        if (rc == AMT_OK && d->sumflux_n) rc = amt_sumflux_accumulate_domain("amt_domain_step", d, 1);
-        if (rc == AMT_OK && d->guard_every) rc = amt_diag_after_sweep("amt_domain_step", d, 1);
+        int rc = d->cyclic ? amt_cyclic_refresh_domain(who, d, d->cyclic, members) : AMT_OK;
+        // every member in one launch; a domain takes the single-patch launch, an ensemble the stacked one also for one member
+        if (rc == AMT_OK)
+            rc = stacked ? amt_device_call_ensemble<T>(d->stream, d->variant, members, a)
+                         : amt_device_call<T>(d->stream, d->variant, a);
+        if (rc == AMT_OK) rc = amt_handle_behind_sweep(who, d, members);
+        if (rc == AMT_OK && d->guard_every) rc = amt_diag_after_sweep(who, d, members);
         if (rc) return rc;
     }
     return AMT_OK;
 }
 
-extern "C" int amt_domain_cyclic_fill(amt_domain *d, int axes)
+// Sweeps that are scaffolding (the placement sampling's timed ones): an armed non-finite guard neither checks nor counts them
+// (and does not stretch them), nor does the boundary-zone update follow them, nor a flux accumulation (its counter and
+// accumulators stay as they are).  The settings of the sequence above that such sweeps must not see are saved and restored here.
+struct StepExtrasPause {
+    amt_domain *d;
+    int every, spec_bdy, sumflux_n;
+    explicit StepExtrasPause(amt_domain *dom) : d(dom), every(dom->guard_every), spec_bdy(dom->spec_bdy), sumflux_n(dom->sumflux_n)
+    {
+        d->guard_every = 0; d->spec_bdy = 0; d->sumflux_n = 0;
+    }
+    ~StepExtrasPause() { d->guard_every = every; d->spec_bdy = spec_bdy; d->sumflux_n = sumflux_n; }
+};
+}  // namespace
+
+int amt_handle_step(const char *who, amt_domain *d, int members, bool stacked, int n_sweeps)
 {
-    if (!d) return amt_fail(AMT_ERR_INVALID_ARG, "null domain");
     DeviceScope scope(d->device);
-    return amt_cyclic_refresh_domain("amt_domain_cyclic_fill", d, axes, 1);
+    return d->dtype_bytes == 8 ? handle_step_t<double>(who, d, members, stacked, n_sweeps)
+                               : handle_step_t<float>(who, d, members, stacked, n_sweeps);
 }
 
-extern "C" int amt_domain_set_cyclic(amt_domain *d, int axes)
+int amt_handle_step_timed(const char *who_step, const char *who, amt_domain *d, int members, bool stacked, int n_sweeps,
+                          float *ms_total)
 {
-    if (!d) return amt_fail(AMT_ERR_INVALID_ARG, "null domain");
-    const int rc = amt_cyclic_check_domain("amt_domain_set_cyclic", d, axes, 1);
-    if (rc == AMT_OK) d->cyclic = axes;
-    return rc;
-}
-
-extern "C" int amt_domain_cyclic(const amt_domain *d) { return d ? d->cyclic : 0; }
-
-extern "C" int amt_domain_spec_bdy_update(amt_domain *d)
-{
-    if (!d) return amt_fail(AMT_ERR_INVALID_ARG, "null domain");
-    DeviceScope scope(d->device);
-    return amt_bdy_update_domain("amt_domain_spec_bdy_update", d, 1);
-}
-
-extern "C" int amt_domain_set_spec_bdy(amt_domain *d, int on)
-{
-    if (!d) return amt_fail(AMT_ERR_INVALID_ARG, "null domain");
-    if (!on) { d->spec_bdy = 0; return AMT_OK; }
-    const int rc = amt_bdy_check_domain("amt_domain_set_spec_bdy", d, 1);
-    if (rc == AMT_OK) d->spec_bdy = 1;
-    return rc;
-}
-
-extern "C" int amt_domain_spec_bdy(const amt_domain *d) { return d ? d->spec_bdy : 0; }
-
-extern "C" int amt_domain_step(amt_domain *d, int n_sweeps)
-{
-    if (!d || n_sweeps < 0) return amt_fail(AMT_ERR_INVALID_ARG, "bad step argument");
-    DeviceScope scope(d->device);
-    return d->dtype_bytes == 8 ? amt_domain_step_t<double>(d, n_sweeps) : amt_domain_step_t<float>(d, n_sweeps);
-}
-
-extern "C" int amt_domain_step_timed(amt_domain *d, int n_sweeps, float *ms_total)
-{
-    if (!d || n_sweeps < 0) return amt_fail(AMT_ERR_INVALID_ARG, "bad step argument");
     DeviceScope scope(d->device);
     AMT_HIP(hipEventRecord(d->ev0, d->stream));
-    int rc = amt_domain_step(d, n_sweeps);
+    int rc = amt_handle_step(who_step, d, members, stacked, n_sweeps);
     if (rc) return rc;
     AMT_HIP(hipEventRecord(d->ev1, d->stream));
     AMT_HIP(hipEventSynchronize(d->ev1));
     float ms = 0.f;
     AMT_HIP(hipEventElapsedTime(&ms, d->ev0, d->ev1));
     if (ms_total) *ms_total = ms;
-    return d->guard_every ? amt_diag_guard_status("amt_domain_step_timed", d) : AMT_OK;
+    return d->guard_every ? amt_diag_guard_status(who, d) : AMT_OK;
+}
+
+int amt_handle_sync(const char *who, amt_domain *d)
+{
+    DeviceScope scope(d->device);
+    AMT_HIP(hipStreamSynchronize(d->stream));
+    return d->guard_every ? amt_diag_guard_status(who, d) : AMT_OK;
+}
+
+int amt_handle_cyclic_fill(const char *who, amt_domain *d, int members, int axes)
+{
+    DeviceScope scope(d->device);
+    return amt_cyclic_refresh_domain(who, d, axes, members);
+}
+
+int amt_handle_set_cyclic(const char *who, amt_domain *d, int members, int axes)
+{
+    const int rc = amt_cyclic_check_domain(who, d, axes, members);
+    if (rc == AMT_OK) d->cyclic = axes;
+    return rc;
+}
+
+int amt_handle_spec_bdy_update(const char *who, amt_domain *d, int members)
+{
+    DeviceScope scope(d->device);
+    return amt_bdy_update_domain(who, d, members);
+}
+
+int amt_handle_set_spec_bdy(const char *who, amt_domain *d, int members, int on)
+{
+    const int rc = on ? amt_bdy_check_domain(who, d, members) : AMT_OK;
+    if (rc == AMT_OK) d->spec_bdy = on ? 1 : 0;
+    return rc;
+}
+
+void *amt_handle_field_ptr(amt_domain *d, int field) { return field < 0 || field >= AMT_F_COUNT ? nullptr : d->field[field]; }
+
+extern "C" int amt_domain_cyclic_fill(amt_domain *d, int axes)
+{
+    return d ? amt_handle_cyclic_fill("amt_domain_cyclic_fill", d, 1, axes) : amt_null_domain();
+}
+extern "C" int amt_domain_set_cyclic(amt_domain *d, int axes)
+{
+    return d ? amt_handle_set_cyclic("amt_domain_set_cyclic", d, 1, axes) : amt_null_domain();
+}
+extern "C" int amt_domain_cyclic(const amt_domain *d) { return d ? d->cyclic : 0; }
+extern "C" int amt_domain_spec_bdy_update(amt_domain *d)
+{
+    return d ? amt_handle_spec_bdy_update("amt_domain_spec_bdy_update", d, 1) : amt_null_domain();
+}
+extern "C" int amt_domain_set_spec_bdy(amt_domain *d, int on)
+{
+    return d ? amt_handle_set_spec_bdy("amt_domain_set_spec_bdy", d, 1, on) : amt_null_domain();
+}
+extern "C" int amt_domain_spec_bdy(const amt_domain *d) { return d ? d->spec_bdy : 0; }
+
+extern "C" int amt_domain_step(amt_domain *d, int n_sweeps)
+{
+    if (!d || n_sweeps < 0) return amt_fail(AMT_ERR_INVALID_ARG, "bad step argument");
+    return amt_handle_step("amt_domain_step", d, 1, false, n_sweeps);
+}
+
+extern "C" int amt_domain_step_timed(amt_domain *d, int n_sweeps, float *ms_total)
+{
+    if (!d || n_sweeps < 0) return amt_fail(AMT_ERR_INVALID_ARG, "bad step argument");
+    return amt_handle_step_timed("amt_domain_step", "amt_domain_step_timed", d, 1, false, n_sweeps, ms_total);
 }
 
 // Placement tuning.  Where the driver puts an array's pages moves the sweep by up to +-3 % (same kernel, same virtual
@@ -404,17 +464,7 @@ extern "C" int amt_domain_step_timed(amt_domain *d, int n_sweeps, float *ms_tota
 static int amt_domain_tune(amt_domain *d, int tries, float *ms_per_try, bool preserve)
 {
     DeviceScope scope(d->device);
-    // the timed sweeps are scaffolding: an armed non-finite guard neither checks nor counts them (and does not stretch them)
-    // nor does the boundary-zone update follow them, nor a flux accumulation (its counter and accumulators stay as they are)
-    struct StepExtrasPause {
-        amt_domain *d;
-        int every, spec_bdy, sumflux_n;
-        explicit StepExtrasPause(amt_domain *dom) : d(dom), every(dom->guard_every), spec_bdy(dom->spec_bdy), sumflux_n(dom->sumflux_n)
-        {
-            d->guard_every = 0; d->spec_bdy = 0; d->sumflux_n = 0;
-        }
-        ~StepExtrasPause() { d->guard_every = every; d->spec_bdy = spec_bdy; d->sumflux_n = sumflux_n; }
-    } pause(d);
+    StepExtrasPause pause(d);                                     // the timed sweeps are scaffolding
     auto bytes = [&](int f) { return d->count(f) * (size_t)d->dtype_bytes; };
     auto time_current = [&](float *ms) -> int {
         int rc = amt_domain_step(d, 1);
@@ -517,19 +567,6 @@ extern "C" int amt_domain_placement(const amt_domain *d, float *ms_per_try, int 
     return d->placement_tries;
 }
 
-extern "C" int amt_domain_sync(amt_domain *d)
-{
-    if (!d) return amt_fail(AMT_ERR_INVALID_ARG, "null domain");
-    DeviceScope scope(d->device);
-    AMT_HIP(hipStreamSynchronize(d->stream));
-    return d->guard_every ? amt_diag_guard_status("amt_domain_sync", d) : AMT_OK;
-}
-
-extern "C" void *amt_domain_field_ptr(amt_domain *d, int field)
-{
-    if (!d || field < 0 || field >= AMT_F_COUNT) return nullptr;
-    return d->field[field];
-}
-
+extern "C" int amt_domain_sync(amt_domain *d) { return d ? amt_handle_sync("amt_domain_sync", d) : amt_null_domain(); }
+extern "C" void *amt_domain_field_ptr(amt_domain *d, int field) { return d ? amt_handle_field_ptr(d, field) : nullptr; }
 extern "C" void *amt_domain_stream(amt_domain *d) { return d ? (void *)d->stream : nullptr; }
-

@@ -151,11 +151,9 @@ int grid_tile(amt_grid *g, hipStream_t stream, int its, int ite, int jts, int jt
 // and a patch that touches no domain edge enqueues nothing.
 // With amt_domain_set_sumflux the flux accumulation of this rank's own tile follows at the same place:
 // its operands are this rank's u, v and the ww the sweep has just written, nothing is exchanged for it either.
-int grid_bdy(amt_grid *g, const char *who)
-{
-    const int rc = g->dom->spec_bdy ? amt_bdy_update_domain(who, g->dom, 1) : AMT_OK;
-    return rc == AMT_OK && g->dom->sumflux_n ? amt_sumflux_accumulate_domain(who, g->dom, 1) : rc;
-}
+// The part of a resident handle's sweep sequence behind the sweep (amt_domain.hip), without the guard check: these steppers do
+// not run the non-finite guard.
+int grid_bdy(amt_grid *g, const char *who) { return amt_handle_behind_sweep(who, g->dom, 1); }
 
 // the cells that read a neighbour's data, after the halos are in: boundary rows over the patch's whole width (they own the
 // corners), boundary columns over the rows in between; every tile is clipped on its own by the routine's window rule
@@ -772,17 +770,13 @@ extern "C" int amt_grid_halo_pack(amt_grid *g) { return g ? external_pack_only(g
 extern "C" int amt_grid_halo_unpack(amt_grid *g) { return g ? external_pack_only(g, true) : amt_fail(AMT_ERR_INVALID_ARG, "null grid"); }
 
 // The planner: the message list of patch (ri, rj) of pi x pj from the shape alone.  Nothing of the device is touched.
-extern "C" int amt_halo_plan(int dtype_bytes, int periodic_x, int specified, int nested, int ids, int ide, int jds, int jde, int kde,
-                             int ims, int ime, int jms, int jme, int kms, int kme, int its, int ite, int jts, int jte, int kts, int kte,
-                             int ri, int rj, int pi, int pj, int flags, amt_halo_message *out, int cap, int *n)
+extern "C" int amt_halo_plan(AMT_SHAPE_SIG, int ri, int rj, int pi, int pj, int flags, amt_halo_message *out, int cap, int *n)
 {
     if (!n || cap < 0 || (cap > 0 && !out)) return amt_fail(AMT_ERR_INVALID_ARG, "amt_halo_plan: bad argument");
     if (dtype_bytes != 4 && dtype_bytes != 8) return amt_fail(AMT_ERR_INVALID_ARG, "amt_halo_plan: dtype_bytes is 4 or 8");
     if (ime < ims || jme < jms || kme < kms) return amt_fail(AMT_ERR_PRECONDITION, "amt_halo_plan: empty memory extents");
     amt_domain d;
-    d.dtype_bytes = dtype_bytes; d.periodic_x = periodic_x; d.specified = specified; d.nested = nested;
-    d.ids = ids; d.ide = ide; d.jds = jds; d.jde = jde; d.kde = kde; d.ims = ims; d.ime = ime; d.jms = jms; d.jme = jme;
-    d.kms = kms; d.kme = kme; d.its = its; d.ite = ite; d.jts = jts; d.jte = jte; d.kts = kts; d.kte = kte;
+    amt_domain_set_shape(&d, AMT_SHAPE_ARGS);
     amt_grid g;
     const int rc = grid_topology(&g, &d, ri, rj, pi, pj, true, flags | AMT_SLAB_TRANSPORT_EXTERNAL, false, false);
     if (rc) return rc;

@@ -203,11 +203,11 @@ struct amt_domain {
 };
 
 // resident ensemble handle (amt_ensemble.hip).  The bounds, flags, scalars, variant, stream and the 26 BASE pointers live in an
-// amt_domain (so that amt_domain_args packs the call); what that struct calls a field's count is ONE member's.
+// amt_domain (so that amt_domain_args packs the call); what that struct calls a field's count is ONE member's: a rank-3 or
+// rank-2 array holds `members` of them, a rank-1 array is shared.
 struct amt_ensemble {
     amt_domain d;
     int members = 1;
-    size_t count(int f) const { return d.count(f) * (amt_field_rank(f) == 1 ? (size_t)1 : (size_t)members); }
 };
 
 template <typename T>
@@ -220,6 +220,59 @@ inline void amt_domain_args(amt_domain *d, AmtArgs<T> &a)
     a.ims = d->ims; a.ime = d->ime; a.jms = d->jms; a.jme = d->jme; a.kms = d->kms; a.kme = d->kme;
     a.its = d->its; a.ite = d->ite; a.jts = d->jts; a.jte = d->jte; a.kts = d->kts; a.kte = d->kte;
 }
+
+// the shape arguments of the create / wrap calls and of amt_halo_plan, in the header's order
+#define AMT_SHAPE_SIG                                                                           \
+    int dtype_bytes, int periodic_x, int specified, int nested,                                 \
+    int ids, int ide, int jds, int jde, int kde,                                                \
+    int ims, int ime, int jms, int jme, int kms, int kme,                                       \
+    int its, int ite, int jts, int jte, int kts, int kte
+#define AMT_SHAPE_ARGS                                                                          \
+    dtype_bytes, periodic_x, specified, nested, ids, ide, jds, jde, kde,                        \
+    ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte
+// Hidden visibility down to the pop: these functions are new, and the library's dynamic symbol table stays what it was.
+// (The older cross-file helpers below -- amt_cyclic_refresh_domain and the rest -- are exported C++ symbols by accident of the
+// default visibility; nothing outside the library may call either kind.)
+#pragma GCC visibility push(hidden)
+void amt_domain_set_shape(amt_domain *d, AMT_SHAPE_SIG);
+
+// ---------------------------------------------------------------------------
+// The bodies under the exports amt_domain_* and amt_ensemble_* (amt_domain.hip).  An ensemble handle is an amt_domain plus a
+// member count, so each is one function of (who, d, members): `who` the export's name for the error texts, `members` 1 for a
+// domain.  The exports keep the null check and the argument checks whose texts differ, and are one call of these otherwise.
+//   amt_handle_open:         behind the argument checks of create / wrap: d (shape set) gets the current device, a stream and
+//                            two events, and adopts `fields` / `hip_stream` or allocates (fields == nullptr); on an error d
+//                            holds nothing
+//   amt_handle_close:        releases everything d holds (the caller deletes the handle)
+//   amt_handle_step:         THE SWEEP SEQUENCE of a resident handle, n_sweeps times: guard status, then per sweep
+//                                [cyclic refresh] -> sweep -> [zone update] -> [accumulation] -> [guard check]
+//                            stacked = false: the single-patch launch amt_device_call (a domain); true: the launch
+//                            amt_device_call_ensemble (an ensemble, also one of a single member).  A per-sweep setting is a
+//                            member at the END of amt_domain, a line of this sequence, and -- when the placement sampling must
+//                            not see it -- a line of StepExtrasPause next to it.
+//   amt_handle_behind_sweep: the part behind the sweep that the grid and slab steppers share with it (amt_grid.hip): zone update,
+//                            then accumulation; NOT the guard check
+//   amt_handle_copy:         device scope, one asynchronous copy between `dev` (inside an array of d) and `host`, stream sync
+//   amt_handle_fill:         the fields of `field_mask` from the generator, member m with seed + m at its offset
+// ---------------------------------------------------------------------------
+int amt_handle_open(const char *who, amt_domain *d, int members, void *const *fields, void *hip_stream);
+void amt_handle_close(amt_domain *d);
+int amt_handle_set_scalars(amt_domain *d, double rdx, double rdy, double dts, double epssm);
+int amt_handle_set_variant(amt_domain *d, int variant);
+int amt_handle_step(const char *who, amt_domain *d, int members, bool stacked, int n_sweeps);
+int amt_handle_step_timed(const char *who_step, const char *who, amt_domain *d, int members, bool stacked, int n_sweeps,
+                          float *ms_total);
+int amt_handle_behind_sweep(const char *who, amt_domain *d, int members);
+int amt_handle_sync(const char *who, amt_domain *d);
+int amt_handle_cyclic_fill(const char *who, amt_domain *d, int members, int axes);
+int amt_handle_set_cyclic(const char *who, amt_domain *d, int members, int axes);
+int amt_handle_spec_bdy_update(const char *who, amt_domain *d, int members);
+int amt_handle_set_spec_bdy(const char *who, amt_domain *d, int members, int on);
+void *amt_handle_field_ptr(amt_domain *d, int field);
+int amt_handle_copy(amt_domain *d, void *dev, void *host, size_t bytes, bool up);
+int amt_handle_fill(amt_domain *d, int members, uint64_t field_mask, uint64_t seed,
+                    long gi0, long gk0, long gj0, long gidim, long gkdim, long gjdim);
+#pragma GCC visibility pop
 
 // ---------------------------------------------------------------------------
 // cyclic lateral boundaries (amt_cyclic.hip): one refresh of `members` member-stacked patches of the domain's shape on the

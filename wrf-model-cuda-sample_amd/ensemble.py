@@ -99,7 +99,7 @@ def advance_mu_t_ensemble(ww, ww_1, u, u_1, v, v_1, mu, mut, muave, muts, muu, m
     _lib.check(status)
 
 
-class Ensemble(_lib.HandleDiag):
+class Ensemble(_lib.ResidentHandle):
     """Resident ensemble handle (``amt_ensemble_*``).  ``Ensemble(b, members, ...)`` lets the library allocate the stacked
     arrays on the current device; ``Ensemble.wrap(arrays, b, ...)`` steps the caller's torch tensors in place."""
 
@@ -141,12 +141,6 @@ class Ensemble(_lib.HandleDiag):
                        _fields=[arrays[n].data_ptr() for n in _S.FIELD_NAMES], _stream=handle,
                        _keep=(dict(arrays), stream))
 
-    def set_scalars(self, rdx, rdy, dts, epssm) -> None:
-        _lib.check(self.L.amt_ensemble_set_scalars(self.handle, float(rdx), float(rdy), float(dts), float(epssm)))
-
-    def set_variant(self, variant: int) -> None:
-        _lib.check(self.L.amt_ensemble_set_variant(self.handle, int(variant)))
-
     def _host(self, name: str, a) -> np.ndarray:
         if not (isinstance(a, np.ndarray) and a.dtype == self.dtype and a.flags["C_CONTIGUOUS"]
                 and tuple(a.shape) == tuple(self.bounds.shape(name))):
@@ -178,38 +172,6 @@ class Ensemble(_lib.HandleDiag):
         _lib.check(self.L.amt_ensemble_fill_synthetic(self.handle, ctypes.c_uint64(int(seed)), b.ims, b.kms - 1, b.jms,
                                                       gni + 2, gnk + 1, gnj + 2))
 
-    def step(self, n_sweeps: int = 1) -> None:
-        self._check(self.L.amt_ensemble_step(self.handle, int(n_sweeps)))
-
-    def step_timed(self, n_sweeps: int = 1) -> float:
-        ms = ctypes.c_float()
-        self._check(self.L.amt_ensemble_step_timed(self.handle, int(n_sweeps), ctypes.byref(ms)))
-        return float(ms.value)
-
-    def set_cyclic(self, axes: int) -> None:
-        """``amt_ensemble_set_cyclic``: CYCLIC_X | CYCLIC_Y of api.py; every sweep of ``step`` / ``step_timed`` is then preceded
-        by one refresh launch over all members.  0 = off."""
-        _lib.check(self.L.amt_ensemble_set_cyclic(self.handle, int(axes)))
-
-    def cyclic(self) -> int:
-        return int(self.L.amt_ensemble_cyclic(self.handle))
-
-    def cyclic_fill(self, axes: int) -> None:
-        """``amt_ensemble_cyclic_fill``: one refresh of every member now, asynchronous on the handle's stream."""
-        _lib.check(self.L.amt_ensemble_cyclic_fill(self.handle, int(axes)))
-
-    def set_spec_bdy(self, on: bool = True) -> None:
-        """``amt_ensemble_set_spec_bdy``: every sweep of ``step`` / ``step_timed`` is then followed by one launch that advances the
-        boundary zone of every member (specified / nested domains, header section 12).  False = off."""
-        _lib.check(self.L.amt_ensemble_set_spec_bdy(self.handle, int(bool(on))))
-
-    def spec_bdy(self) -> bool:
-        return bool(self.L.amt_ensemble_spec_bdy(self.handle))
-
-    def spec_bdy_update(self) -> None:
-        """``amt_ensemble_spec_bdy_update``: one update of every member now, asynchronous on the handle's stream."""
-        _lib.check(self.L.amt_ensemble_spec_bdy_update(self.handle))
-
     def moments(self, field, region="window", want=("mean", "var"), out=None) -> dict:
         """``amt_ensemble_moments``: mean, sample variance, minimum and maximum over the members of ``field`` (a name or an
         ``amt_field`` id, rank 2 or 3) over ``region`` ("window" / "memory" or REGION_*), as torch tensors of ONE member's shape
@@ -227,24 +189,6 @@ class Ensemble(_lib.HandleDiag):
         _lib.check(self.L.amt_ensemble_moments(self.handle, _S.FIELD_ID[name], int(region), *ptrs))
         return res
 
-    def sync(self) -> None:
-        self._check(self.L.amt_ensemble_sync(self.handle))
-
-    def field_ptr(self, name: str) -> int:
-        return int(self.L.amt_ensemble_field_ptr(self.handle, _S.FIELD_ID[name]) or 0)
-
-    @property
-    def stream(self) -> int:
-        return int(self.L.amt_ensemble_stream(self.handle) or 0)
-
     def close(self) -> None:
-        if self.handle:
-            self.L.amt_ensemble_destroy(self.handle)
-            self.handle = ctypes.c_void_p()
+        super().close()
         self._keep = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

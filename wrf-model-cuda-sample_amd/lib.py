@@ -266,10 +266,21 @@ def check(status: int) -> None:
         raise AmtError(status, msg)
 
 
-class HandleDiag:
-    """``field_stats / compare / set_guard / guard_report`` of a resident handle (header section 10).  The owning class names
-    its C functions' prefix (``amt_domain`` / ``amt_ensemble``) in ``_PREFIX`` and its member count in ``_members()``; its
-    stepping methods pass their status through ``_check`` so that an ERR_NONFINITE error carries the guard's report."""
+class DeviceView:
+    """Device memory the library owns, for ``torch.as_tensor``: a ``__cuda_array_interface__`` over ``ptr`` that keeps ``owner`` --
+    the Python object whose handle owns the memory -- alive for as long as a tensor views it."""
+
+    def __init__(self, owner, ptr: int, shape, typestr: str):
+        self.owner = owner
+        self.__cuda_array_interface__ = {"shape": tuple(int(n) for n in shape), "typestr": typestr, "data": (int(ptr), False),
+                                         "version": 2, "strides": None}
+
+
+class ResidentHandle:
+    """What a resident handle does whichever kind it is (header sections 4, 8, 9, 10, 12, 14): stepping, the per-sweep settings,
+    the diagnostics and the release.  The owning class names its C functions' prefix (``amt_domain`` / ``amt_ensemble``) in
+    ``_PREFIX`` and its member count in ``_members()``, and holds the library in ``L`` and the handle in ``handle``.  The stepping
+    methods pass their status through ``_check`` so that an ERR_NONFINITE error carries the guard's report."""
     _PREFIX = "amt_domain"
 
     def _members(self) -> int:
@@ -283,6 +294,70 @@ class HandleDiag:
             msg = self.L.amt_last_error().decode()
             raise AmtError(status, msg, report=self.guard_report())
         check(status)
+
+    def set_scalars(self, rdx, rdy, dts, epssm) -> None:
+        check(self._fn("set_scalars")(self.handle, float(rdx), float(rdy), float(dts), float(epssm)))
+
+    def set_variant(self, variant: int) -> None:
+        check(self._fn("set_variant")(self.handle, int(variant)))
+
+    def step(self, n_sweeps: int = 1) -> None:
+        """``step``: asynchronous on the handle's stream; every member of an ensemble in one launch per sweep."""
+        self._check(self._fn("step")(self.handle, int(n_sweeps)))
+
+    def step_timed(self, n_sweeps: int = 1) -> float:
+        ms = ctypes.c_float()
+        self._check(self._fn("step_timed")(self.handle, int(n_sweeps), ctypes.byref(ms)))
+        return float(ms.value)
+
+    def sync(self) -> None:
+        self._check(self._fn("sync")(self.handle))
+
+    def set_cyclic(self, axes: int) -> None:
+        """``set_cyclic``: CYCLIC_X | CYCLIC_Y of api.py; every sweep of ``step`` / ``step_timed`` is then preceded by a refresh
+        of the wrap cells (one launch over all members).  0 = off."""
+        check(self._fn("set_cyclic")(self.handle, int(axes)))
+
+    def cyclic(self) -> int:
+        return int(self._fn("cyclic")(self.handle))
+
+    def cyclic_fill(self, axes: int) -> None:
+        """``cyclic_fill``: one refresh (of every member) now, asynchronous on the handle's stream."""
+        check(self._fn("cyclic_fill")(self.handle, int(axes)))
+
+    def set_spec_bdy(self, on: bool = True) -> None:
+        """``set_spec_bdy``: every sweep of ``step`` / ``step_timed`` is then followed by the boundary-zone update of a specified /
+        nested domain (header section 12; one launch over all members).  False = off."""
+        check(self._fn("set_spec_bdy")(self.handle, int(bool(on))))
+
+    def spec_bdy(self) -> bool:
+        return bool(self._fn("spec_bdy")(self.handle))
+
+    def spec_bdy_update(self) -> None:
+        """``spec_bdy_update``: one update (of every member) now, asynchronous on the handle's stream."""
+        check(self._fn("spec_bdy_update")(self.handle))
+
+    def field_ptr(self, field) -> int:
+        """Device address of the array of ``field`` (a name or an ``amt_field`` id); 0 for an id that names none."""
+        if isinstance(field, str):
+            from .synth import FIELD_ID
+            field = FIELD_ID[field]
+        return int(self._fn("field_ptr")(self.handle, int(field)) or 0)
+
+    @property
+    def stream(self) -> int:
+        return int(self._fn("stream")(self.handle) or 0)
+
+    def close(self) -> None:
+        if self.handle:
+            self._fn("destroy")(self.handle)
+            self.handle = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
     def field_stats(self, field: int, region: int = REGION_WINDOW):
         """``FieldStats`` of ``field`` (enum amt_field) over ``region``; an ensemble returns a list, one per member."""
@@ -327,3 +402,6 @@ class HandleDiag:
     def sumflux_ptr(self, which: int) -> int:
         """Device address of ru_m (0), rv_m (1) or ww_m (2); 0 while the setting is off."""
         return int(self._fn("sumflux_ptr")(self.handle, int(which)) or 0)
+
+
+HandleDiag = ResidentHandle          # the name this class had while it held the diagnostics only

@@ -380,24 +380,97 @@ class GridStepper:
             self.compute(*args)
 
 
-def _substep_inputs(stepper, dom, seed, sweep, sides):
-    """amt_domain_fill_fields(AMT_EXCHANGED_FIELDS, seed + sweep) [+ amt_domain_poison_halos(sides)] on the domain's stream."""
-    b = stepper.patch.bounds
-    gdims = stepper.patch.global_dims or (b.ide - b.ids, b.kde - 1, b.jde - b.jds)
-    mask = 0
-    for name in _S.EXCHANGED_INPUTS:
-        mask |= 1 << _S.FIELD_ID[name]
-    with stepper._dev():
-        stepper._lib.check(stepper.L.amt_domain_fill_fields(dom, mask, _S.sweep_seed(seed, sweep), b.ims, b.kms - 1, b.jms,
-                                                            gdims[0] + 2, gdims[1] + 1, gdims[2] + 2))
-        if sides:
-            stepper._lib.check(stepper.L.amt_domain_poison_halos(dom, sides))
+class _NativeStepper:
+    """What the steppers over the C++ runtime share.  The 26 torch CUDA tensors of ``patch`` stay the owners: ``_open`` wraps
+    them in an ``amt_domain_wrap`` handle (``_dom``) on ``stream``, configures it, and makes the stepper's own handle (``_h``)
+    with ``<_HANDLE>_create``.  A subclass names the prefix of its handle's C functions in ``_HANDLE`` and sets ``cyclic`` and
+    ``_halo_sides`` before it calls ``_open``."""
 
+    NO_OVERLAP, LOOPBACK, TRANSPORT_IPC = 1, 2, 4          # enum amt_slab_flags
+    _HANDLE = "amt_grid"
 
-class _SumfluxOfStepper:
-    """``sumflux=n`` of the native steppers (header section 14): every sweep is followed by one accumulation of this rank's own
-    tile into ru_m, rv_m, ww_m, which the library allocates; the counter runs 1..n and wraps.  Nothing is exchanged for it."""
+    def _open(self, patch: Patch, rank_args, flags: int, *, overlap, stream, variant, spec_bdy, sumflux, transport=None, unique_id=None):
+        import ctypes
+        import torch
+        from . import lib as _lib
+        from .synth import FIELD_NAMES
+        self._lib, self._ct = _lib, ctypes
+        self.L = L = _lib.load_library()
+        self.patch = patch
+        t0 = patch.arrays["t_1"]
+        if not t0.is_cuda:
+            raise TypeError(f"{type(self).__name__} needs a device patch (there is no CPU path)")
+        if transport not in (None, "rccl", "ipc"):
+            raise ValueError("transport is 'rccl' or 'ipc'")
+        b = patch.bounds
+        for name in FIELD_NAMES:
+            t = patch.arrays[name]
+            if not (t.is_cuda and t.dtype == t0.dtype and t.is_contiguous() and tuple(t.shape) == tuple(b.shape(name))):
+                raise TypeError(f"{name}: need a contiguous device tensor of shape {b.shape(name)}")
+        self.stream = stream if stream is not None else torch.cuda.Stream(device=t0.device)
+        self.device_index = t0.device.index if t0.device.index is not None else torch.cuda.current_device()
+        fields = (ctypes.c_void_p * len(FIELD_NAMES))(*[patch.arrays[n].data_ptr() for n in FIELD_NAMES])
+        self.flags = (flags | (0 if overlap else self.NO_OVERLAP) | (self.TRANSPORT_IPC if transport == "ipc" else 0)
+                      | (CYCLIC_X_FLAG if self.cyclic[0] else 0) | (CYCLIC_Y_FLAG if self.cyclic[1] else 0))
+        self._dom, self._h = ctypes.c_void_p(), ctypes.c_void_p()
+        with self._dev():
+            _lib.check(L.amt_domain_wrap(ctypes.byref(self._dom), t0.element_size(), *patch.config.as_ints(),
+                                         *b.as_tuple(), fields, ctypes.c_void_p(self.stream.cuda_stream)))
+            try:
+                _lib.check(L.amt_domain_set_scalars(self._dom, patch.rdx, patch.rdy, patch.dts, patch.epssm))
+                _lib.check(L.amt_domain_set_variant(self._dom, int(variant)))
+                if spec_bdy:                                  # the boundary-zone update behind every sweep (header section 12)
+                    _lib.check(L.amt_domain_set_spec_bdy(self._dom, 1))
+                if sumflux:                                   # the flux averages behind every sweep (header section 14)
+                    _lib.check(L.amt_domain_set_sumflux(self._dom, int(sumflux), None, None, None))
+                uid = None
+                if unique_id is not None:
+                    uid = (ctypes.c_char * 128).from_buffer_copy(bytes(unique_id))
+                _lib.check(getattr(L, f"{self._HANDLE}_create")(ctypes.byref(self._h), self._dom, *rank_args, uid, self.flags))
+            except BaseException:
+                L.amt_domain_destroy(self._dom)
+                self._dom = ctypes.c_void_p()
+                raise
 
+    def _dev(self):
+        import torch
+        return torch.cuda.device(self.device_index)
+
+    def _fn(self, name: str):
+        return getattr(self.L, f"{self._HANDLE}_{name}")
+
+    def _call(self, name: str, *args):
+        with self._dev():
+            self._lib.check(self._fn(name)(self._h, *args))
+
+    def sync(self):
+        self._call("sync")
+
+    def next_substep_inputs(self, seed: int, sweep: int, poison: bool = True):
+        """What a host model does between two calls: new values in the fields that cross a patch boundary (the stand-in for
+        advance_uv: amt_domain_fill_fields with AMT_EXCHANGED_FIELDS, seed + sweep) and, for verification, NaN in the halo
+        rows and columns (amt_domain_poison_halos) -- both on the domain's stream.  Only an exchange that delivers THIS
+        sweep's halos then gives the bits of the unsplit run."""
+        b = self.patch.bounds
+        gdims = self.patch.global_dims or (b.ide - b.ids, b.kde - 1, b.jde - b.jds)
+        mask = 0
+        for name in _S.EXCHANGED_INPUTS:
+            mask |= 1 << _S.FIELD_ID[name]
+        with self._dev():
+            self._lib.check(self.L.amt_domain_fill_fields(self._dom, mask, _S.sweep_seed(seed, sweep), b.ims, b.kms - 1, b.jms,
+                                                          gdims[0] + 2, gdims[1] + 1, gdims[2] + 2))
+            if poison and self._halo_sides:
+                self._lib.check(self.L.amt_domain_poison_halos(self._dom, self._halo_sides))
+
+    def halo_bytes_per_sweep(self) -> int:
+        return int(self._fn("halo_bytes")(self._h))                  # sent + received
+
+    def transport(self) -> str:
+        """'rccl', 'ipc', 'external' or 'none' -- what carries this stepper's halos (amt_slab_transport / amt_grid_transport)."""
+        return self._fn("transport")(self._h).decode()
+
+    # ``sumflux=n`` (header section 14): every sweep is followed by one accumulation of this rank's own tile into ru_m, rv_m,
+    # ww_m, which the library allocates; the counter runs 1..n and wraps.  Nothing is exchanged for it.
     def sumflux_state(self):
         """(n_small_steps, next_iteration); n_small_steps = 0: off."""
         n, nxt = self._ct.c_int(), self._ct.c_int()
@@ -413,18 +486,60 @@ class _SumfluxOfStepper:
             ptr = self.L.amt_domain_sumflux_ptr(self._dom, which)
             if not ptr:
                 raise self._lib.AmtError(self._lib.ERR_INVALID_ARG, "the flux averages are off")
-
-            class _View:
-                pass
-            v = _View()
-            v.owner = self
-            v.__cuda_array_interface__ = {"shape": tuple(b.shape("ww")), "typestr": "<f8" if t0.element_size() == 8 else "<f4",
-                                          "data": (int(ptr), False), "version": 2, "strides": None}
-            out.append(torch.as_tensor(v, device=t0.device))
+            view = self._lib.DeviceView(self, ptr, b.shape("ww"), "<f8" if t0.element_size() == 8 else "<f4")
+            out.append(torch.as_tensor(view, device=t0.device))
         return tuple(out)
 
+    def close(self):
+        if self._h:
+            with self._dev():
+                self._fn("destroy")(self._h)
+            self._h = self._ct.c_void_p()
+        if self._dom:
+            self.L.amt_domain_destroy(self._dom)
+            self._dom = self._ct.c_void_p()
 
-class NativeSlabStepper(_SumfluxOfStepper):
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _NativeCommStepper(_NativeStepper):
+    """The steppers whose halos the library moves itself (RCCL or IPC): whole sweeps in one call."""
+
+    @staticmethod
+    def comm_unique_id() -> bytes:
+        """Rank 0: a fresh communicator id to hand to every rank (ncclGetUniqueId)."""
+        import ctypes
+        from . import lib as _lib
+        uid = (ctypes.c_char * 128)()
+        _lib.check(_lib.load_library().amt_comm_unique_id(uid))
+        return bytes(uid)
+
+    def step(self, n_sweeps: int = 1):
+        self._call("step", int(n_sweeps))
+
+    def exchange_halos(self):
+        self._call("exchange")
+
+    def set_skew_us(self, microseconds: int):
+        """Test hook: every later sweep's exchange starts this late on the communication stream (neighbour skew)."""
+        self._lib.check(self._fn("set_skew_us")(self._h, int(microseconds)))
+
+    def pull_mode(self) -> str:
+        """IPC transport: 'copy engine' or 'fused kernel' (amt_slab_pull_mode / amt_grid_pull_mode); '' with RCCL."""
+        return self._fn("pull_mode")(self._h).decode()
+
+    def comm_info(self):
+        """(rank, world) as the transport reports them (communicator / ranks attached to the IPC block); (0, 1) without one."""
+        r, w = self._ct.c_int(), self._ct.c_int()
+        self._lib.check(self._fn("comm_info")(self._h, self._ct.byref(r), self._ct.byref(w)))
+        return r.value, w.value
+
+
+class NativeSlabStepper(_NativeCommStepper):
     """The same j-slab sweep as ``SlabStepper`` driven by the C++ runtime behind the C-ABI
     (``amt_slab_*``, include/amt_advance_mu_t.h section 5): ``ncclSend/ncclRecv`` of the halo rows
     in one RCCL group on a communication stream, the two edge rows behind them on that stream, the
@@ -441,234 +556,38 @@ class NativeSlabStepper(_SumfluxOfStepper):
     header section 12; specified / nested domains).
     """
 
-    NO_OVERLAP, LOOPBACK, TRANSPORT_IPC = 1, 2, 4          # enum amt_slab_flags
+    _HANDLE = "amt_slab"
+    _slab = property(lambda self: self._h)
 
     def __init__(self, patch: Patch, rank: int, world: int, unique_id: Optional[bytes] = None, *,
                  stream=None, overlap: bool = True, variant: int = 0, loopback: bool = False, transport: str = "rccl",
                  cyclic=(False, False), spec_bdy: bool = False, sumflux: int = 0):
-        import ctypes
-        import torch
-        from . import lib as _lib
-        from .synth import FIELD_NAMES
-        self._lib, self._ct = _lib, ctypes
-        self.L = L = _lib.load_library()
-        self.patch, self.rank, self.world = patch, rank, world
+        self.rank, self.world = rank, world
         self.cyclic = (bool(cyclic[0]), bool(cyclic[1]))      # AMT_SLAB_CYCLIC_X / _Y: x is a self wrap of the slab, y a torus
         self.below: Optional[int] = rank - 1 if rank > 0 else None
         self.above: Optional[int] = rank + 1 if rank < world - 1 else None
         self._halo_sides = (_S.SIDE_BELOW | _S.SIDE_ABOVE) if loopback else cyclic_sides(0, rank, 1, world, self.cyclic)
-        t0 = patch.arrays["t_1"]
-        if not t0.is_cuda:
-            raise TypeError("NativeSlabStepper needs a device patch (there is no CPU path)")
-        b = patch.bounds
-        for name in FIELD_NAMES:
-            t = patch.arrays[name]
-            if not (t.is_cuda and t.dtype == t0.dtype and t.is_contiguous() and tuple(t.shape) == tuple(b.shape(name))):
-                raise TypeError(f"{name}: need a contiguous device tensor of shape {b.shape(name)}")
-        self.stream = stream if stream is not None else torch.cuda.Stream(device=t0.device)
-        self.device_index = t0.device.index if t0.device.index is not None else torch.cuda.current_device()
-        fields = (ctypes.c_void_p * len(FIELD_NAMES))(*[patch.arrays[n].data_ptr() for n in FIELD_NAMES])
-        self._dom, self._slab = ctypes.c_void_p(), ctypes.c_void_p()
-        with torch.cuda.device(self.device_index):
-            _lib.check(L.amt_domain_wrap(ctypes.byref(self._dom), t0.element_size(), *patch.config.as_ints(),
-                                         *b.as_tuple(), fields, ctypes.c_void_p(self.stream.cuda_stream)))
-            try:
-                _lib.check(L.amt_domain_set_scalars(self._dom, patch.rdx, patch.rdy, patch.dts, patch.epssm))
-                _lib.check(L.amt_domain_set_variant(self._dom, int(variant)))
-                if spec_bdy:                                  # the boundary-zone update behind every sweep (header section 12)
-                    _lib.check(L.amt_domain_set_spec_bdy(self._dom, 1))
-                if sumflux:                                   # the flux averages behind every sweep (header section 14)
-                    _lib.check(L.amt_domain_set_sumflux(self._dom, int(sumflux), None, None, None))
-                if transport not in ("rccl", "ipc"):
-                    raise ValueError("transport is 'rccl' or 'ipc'")
-                flags = ((0 if overlap else self.NO_OVERLAP) | (self.LOOPBACK if loopback else 0)
-                         | (self.TRANSPORT_IPC if transport == "ipc" else 0)
-                         | (CYCLIC_X_FLAG if self.cyclic[0] else 0) | (CYCLIC_Y_FLAG if self.cyclic[1] else 0))
-                uid = None
-                if unique_id is not None:
-                    uid = (ctypes.c_char * 128).from_buffer_copy(bytes(unique_id))
-                _lib.check(L.amt_slab_create(ctypes.byref(self._slab), self._dom, rank, world, uid, flags))
-            except BaseException:
-                L.amt_domain_destroy(self._dom)
-                self._dom = ctypes.c_void_p()
-                raise
-
-    @staticmethod
-    def comm_unique_id() -> bytes:
-        """Rank 0: a fresh communicator id to hand to every rank (ncclGetUniqueId)."""
-        import ctypes
-        from . import lib as _lib
-        uid = (ctypes.c_char * 128)()
-        _lib.check(_lib.load_library().amt_comm_unique_id(uid))
-        return bytes(uid)
-
-    def _dev(self):
-        import torch
-        return torch.cuda.device(self.device_index)
-
-    def step(self, n_sweeps: int = 1):
-        with self._dev():
-            self._lib.check(self.L.amt_slab_step(self._slab, int(n_sweeps)))
-
-    def exchange_halos(self):
-        with self._dev():
-            self._lib.check(self.L.amt_slab_exchange(self._slab))
-
-    def sync(self):
-        with self._dev():
-            self._lib.check(self.L.amt_slab_sync(self._slab))
-
-    def next_substep_inputs(self, seed: int, sweep: int, poison: bool = True):
-        """What a host model does between two calls: new values in the fields that cross a slab boundary (the stand-in for
-        advance_uv: amt_domain_fill_fields with AMT_EXCHANGED_FIELDS, seed + sweep) and, for verification, NaN in the halo
-        rows (amt_domain_poison_halos) -- both on the domain's stream.  Only an exchange that delivers THIS sweep's rows
-        then gives the bits of the unsplit run."""
-        _substep_inputs(self, self._dom, seed, sweep, self._halo_sides if poison else 0)
-
-    def set_skew_us(self, microseconds: int):
-        """Test hook: every later sweep's exchange starts this late on the communication stream (neighbour skew)."""
-        self._lib.check(self.L.amt_slab_set_skew_us(self._slab, int(microseconds)))
-
-    def halo_bytes_per_sweep(self) -> int:
-        return int(self.L.amt_slab_halo_bytes(self._slab))           # sent + received
-
-    def transport(self) -> str:
-        """'rccl', 'ipc' or 'none' -- what carries this stepper's halo rows (amt_slab_transport)."""
-        return self.L.amt_slab_transport(self._slab).decode()
-
-    def pull_mode(self) -> str:
-        """IPC transport: 'copy engine' or 'fused kernel' (amt_slab_pull_mode); '' with RCCL."""
-        return self.L.amt_slab_pull_mode(self._slab).decode()
-
-    def comm_info(self):
-        """(rank, world) as the transport reports them (communicator / ranks attached to the IPC block); (0, 1) without one."""
-        r, w = self._ct.c_int(), self._ct.c_int()
-        self._lib.check(self.L.amt_slab_comm_info(self._slab, self._ct.byref(r), self._ct.byref(w)))
-        return r.value, w.value
-
-    def close(self):
-        if self._slab:
-            with self._dev():
-                self.L.amt_slab_destroy(self._slab)
-            self._slab = self._ct.c_void_p()
-        if self._dom:
-            self.L.amt_domain_destroy(self._dom)
-            self._dom = self._ct.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open(patch, (rank, world), self.LOOPBACK if loopback else 0, overlap=overlap, stream=stream, variant=variant,
+                   spec_bdy=spec_bdy, sumflux=sumflux, transport=transport, unique_id=unique_id)
 
 
-class NativeGridStepper(_SumfluxOfStepper):
+class NativeGridStepper(_NativeCommStepper):
     """advance_mu_t on patch (ri, rj) of pi x pj driven by the C++ runtime behind the C-ABI (``amt_grid_*``, header section 5b):
     HIP pack / unpack kernels for the strided halo columns, rows and packed columns in ONE exchange (RCCL group or IPC
     pulls), interior cells on the patch's stream beside it, boundary rows and columns behind it on the communication stream.
     Same construction as ``NativeSlabStepper`` (which is its pi = 1 case); rank = rj * pi + ri.
     """
 
-    NO_OVERLAP, LOOPBACK, TRANSPORT_IPC = 1, 2, 4          # enum amt_slab_flags
+    _grid = property(lambda self: self._h)
 
     def __init__(self, patch: Patch, ri: int, rj: int, pi: int, pj: int, unique_id: Optional[bytes] = None, *,
                  stream=None, overlap: bool = True, variant: int = 0, loopback: bool = False, transport: str = "rccl",
                  cyclic=(False, False), spec_bdy: bool = False, sumflux: int = 0):
-        import ctypes
-        import torch
-        from . import lib as _lib
-        from .synth import FIELD_NAMES
-        self._lib, self._ct = _lib, ctypes
-        self.L = L = _lib.load_library()
-        self.patch, self.ri, self.rj, self.pi, self.pj = patch, ri, rj, pi, pj
+        self.ri, self.rj, self.pi, self.pj = ri, rj, pi, pj
         self.cyclic = (bool(cyclic[0]), bool(cyclic[1]))      # AMT_SLAB_CYCLIC_X / _Y
         self._halo_sides = 15 if loopback else cyclic_sides(ri, rj, pi, pj, self.cyclic)
-        t0 = patch.arrays["t_1"]
-        if not t0.is_cuda:
-            raise TypeError("NativeGridStepper needs a device patch (there is no CPU path)")
-        if transport not in ("rccl", "ipc"):
-            raise ValueError("transport is 'rccl' or 'ipc'")
-        b = patch.bounds
-        for name in FIELD_NAMES:
-            t = patch.arrays[name]
-            if not (t.is_cuda and t.dtype == t0.dtype and t.is_contiguous() and tuple(t.shape) == tuple(b.shape(name))):
-                raise TypeError(f"{name}: need a contiguous device tensor of shape {b.shape(name)}")
-        self.stream = stream if stream is not None else torch.cuda.Stream(device=t0.device)
-        self.device_index = t0.device.index if t0.device.index is not None else torch.cuda.current_device()
-        fields = (ctypes.c_void_p * len(FIELD_NAMES))(*[patch.arrays[n].data_ptr() for n in FIELD_NAMES])
-        self._dom, self._grid = ctypes.c_void_p(), ctypes.c_void_p()
-        with torch.cuda.device(self.device_index):
-            _lib.check(L.amt_domain_wrap(ctypes.byref(self._dom), t0.element_size(), *patch.config.as_ints(),
-                                         *b.as_tuple(), fields, ctypes.c_void_p(self.stream.cuda_stream)))
-            try:
-                _lib.check(L.amt_domain_set_scalars(self._dom, patch.rdx, patch.rdy, patch.dts, patch.epssm))
-                _lib.check(L.amt_domain_set_variant(self._dom, int(variant)))
-                if spec_bdy:                                  # the boundary-zone update behind every sweep (header section 12)
-                    _lib.check(L.amt_domain_set_spec_bdy(self._dom, 1))
-                if sumflux:                                   # the flux averages behind every sweep (header section 14)
-                    _lib.check(L.amt_domain_set_sumflux(self._dom, int(sumflux), None, None, None))
-                flags = ((0 if overlap else self.NO_OVERLAP) | (self.LOOPBACK if loopback else 0)
-                         | (self.TRANSPORT_IPC if transport == "ipc" else 0)
-                         | (CYCLIC_X_FLAG if self.cyclic[0] else 0) | (CYCLIC_Y_FLAG if self.cyclic[1] else 0))
-                uid = None
-                if unique_id is not None:
-                    uid = (ctypes.c_char * 128).from_buffer_copy(bytes(unique_id))
-                _lib.check(L.amt_grid_create(ctypes.byref(self._grid), self._dom, ri, rj, pi, pj, uid, flags))
-            except BaseException:
-                L.amt_domain_destroy(self._dom)
-                self._dom = ctypes.c_void_p()
-                raise
-
-    comm_unique_id = staticmethod(NativeSlabStepper.comm_unique_id)
-
-    def _dev(self):
-        import torch
-        return torch.cuda.device(self.device_index)
-
-    def step(self, n_sweeps: int = 1):
-        with self._dev():
-            self._lib.check(self.L.amt_grid_step(self._grid, int(n_sweeps)))
-
-    def exchange_halos(self):
-        with self._dev():
-            self._lib.check(self.L.amt_grid_exchange(self._grid))
-
-    def sync(self):
-        with self._dev():
-            self._lib.check(self.L.amt_grid_sync(self._grid))
-
-    def next_substep_inputs(self, seed: int, sweep: int, poison: bool = True):
-        """As NativeSlabStepper.next_substep_inputs, for the halo rows AND columns of a patch."""
-        _substep_inputs(self, self._dom, seed, sweep, self._halo_sides if poison else 0)
-
-    def halo_bytes_per_sweep(self) -> int:
-        return int(self.L.amt_grid_halo_bytes(self._grid))           # sent + received
-
-    def transport(self) -> str:
-        return self.L.amt_grid_transport(self._grid).decode()
-
-    def pull_mode(self) -> str:
-        return self.L.amt_grid_pull_mode(self._grid).decode()
-
-    def comm_info(self):
-        r, w = self._ct.c_int(), self._ct.c_int()
-        self._lib.check(self.L.amt_grid_comm_info(self._grid, self._ct.byref(r), self._ct.byref(w)))
-        return r.value, w.value
-
-    def close(self):
-        if self._grid:
-            with self._dev():
-                self.L.amt_grid_destroy(self._grid)
-            self._grid = self._ct.c_void_p()
-        if self._dom:
-            self.L.amt_domain_destroy(self._dom)
-            self._dom = self._ct.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open(patch, (ri, rj, pi, pj), self.LOOPBACK if loopback else 0, overlap=overlap, stream=stream, variant=variant,
+                   spec_bdy=spec_bdy, sumflux=sumflux, transport=transport, unique_id=unique_id)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -716,15 +635,6 @@ def halo_layout(bounds, ri: int, rj: int, pi: int, pj: int, cyclic=(False, False
     return out
 
 
-class _LibraryBytes:
-    """``nbytes`` of device memory the library owns at ``ptr``, for torch.as_tensor (as synth.NativeDomain.view); keeps the
-    stepper alive for as long as a tensor views the buffer."""
-
-    def __init__(self, owner, ptr: int, nbytes: int):
-        self.owner = owner
-        self.__cuda_array_interface__ = {"shape": (int(nbytes),), "typestr": "|u1", "data": (int(ptr), False), "version": 2, "strides": None}
-
-
 class HaloMessageView:
     """One side's messages of an external stepper: ``side`` (synth.SIDE_*), ``peer`` (rank), ``send`` / ``recv`` as byte views
     -- torch uint8 device tensors, or numpy uint8 arrays over page-locked host memory (``on_host``)."""
@@ -733,7 +643,7 @@ class HaloMessageView:
         self.side, self.peer, self.send, self.recv, self.on_host = side, peer, send, recv, on_host
 
 
-class ExternalGridStepper(_SumfluxOfStepper):
+class ExternalGridStepper(_NativeStepper):
     """advance_mu_t on patch (ri, rj) of pi x pj with the HOST as the transport (``AMT_SLAB_TRANSPORT_EXTERNAL``): per sweep
     ``begin()`` (pack + interior), ``halo_wait()``, the host copies every ``send`` into the matching ``recv`` of the peer (an
     MPI host: Isend / Irecv with tag = side), ``end()`` (unpack + boundary cells).  Creation is not collective and needs no
@@ -745,58 +655,14 @@ class ExternalGridStepper(_SumfluxOfStepper):
 
     def __init__(self, patch: Patch, ri: int, rj: int, pi: int, pj: int, *, cyclic=(False, False), overlap: bool = True,
                  host_buffers: bool = False, stream=None, variant: int = 0, spec_bdy: bool = False, sumflux: int = 0):
-        import ctypes
-        import torch
-        from . import lib as _lib
-        from .synth import FIELD_NAMES
-        self._lib, self._ct = _lib, ctypes
-        self.L = L = _lib.load_library()
-        self.patch, self.ri, self.rj, self.pi, self.pj = patch, ri, rj, pi, pj
+        self.ri, self.rj, self.pi, self.pj = ri, rj, pi, pj
         self.rank = rj * pi + ri
         self.cyclic = (bool(cyclic[0]), bool(cyclic[1]))
         self.host_buffers = bool(host_buffers)
         self._halo_sides = cyclic_sides(ri, rj, pi, pj, self.cyclic)
-        t0 = patch.arrays["t_1"]
-        if not t0.is_cuda:
-            raise TypeError(f"{type(self).__name__} needs a device patch (there is no CPU path)")
-        b = patch.bounds
-        for name in FIELD_NAMES:
-            t = patch.arrays[name]
-            if not (t.is_cuda and t.dtype == t0.dtype and t.is_contiguous() and tuple(t.shape) == tuple(b.shape(name))):
-                raise TypeError(f"{name}: need a contiguous device tensor of shape {b.shape(name)}")
-        self.stream = stream if stream is not None else torch.cuda.Stream(device=t0.device)
-        self.device_index = t0.device.index if t0.device.index is not None else torch.cuda.current_device()
-        fields = (ctypes.c_void_p * len(FIELD_NAMES))(*[patch.arrays[n].data_ptr() for n in FIELD_NAMES])
-        self._dom, self._h = ctypes.c_void_p(), ctypes.c_void_p()
         self._messages = None
-        with torch.cuda.device(self.device_index):
-            _lib.check(L.amt_domain_wrap(ctypes.byref(self._dom), t0.element_size(), *patch.config.as_ints(),
-                                         *b.as_tuple(), fields, ctypes.c_void_p(self.stream.cuda_stream)))
-            try:
-                _lib.check(L.amt_domain_set_scalars(self._dom, patch.rdx, patch.rdy, patch.dts, patch.epssm))
-                _lib.check(L.amt_domain_set_variant(self._dom, int(variant)))
-                if spec_bdy:                                  # the boundary-zone update behind every sweep (header section 12)
-                    _lib.check(L.amt_domain_set_spec_bdy(self._dom, 1))
-                if sumflux:                                   # the flux averages behind every sweep (header section 14)
-                    _lib.check(L.amt_domain_set_sumflux(self._dom, int(sumflux), None, None, None))
-                self.flags = (EXTERNAL_FLAG | (0 if overlap else 1) | (HOST_BUFFERS_FLAG if host_buffers else 0)
-                              | (CYCLIC_X_FLAG if self.cyclic[0] else 0) | (CYCLIC_Y_FLAG if self.cyclic[1] else 0))
-                if self._SLAB:
-                    _lib.check(L.amt_slab_create(ctypes.byref(self._h), self._dom, rj, pj, None, self.flags))
-                else:
-                    _lib.check(L.amt_grid_create(ctypes.byref(self._h), self._dom, ri, rj, pi, pj, None, self.flags))
-            except BaseException:
-                L.amt_domain_destroy(self._dom)
-                self._dom = ctypes.c_void_p()
-                raise
-
-    def _dev(self):
-        import torch
-        return torch.cuda.device(self.device_index)
-
-    def _call(self, name: str):
-        with self._dev():
-            self._lib.check(getattr(self.L, f"{self._HANDLE}_{name}")(self._h))
+        self._open(patch, (rj, pj) if self._SLAB else (ri, rj, pi, pj), EXTERNAL_FLAG | (HOST_BUFFERS_FLAG if host_buffers else 0),
+                   overlap=overlap, stream=stream, variant=variant, spec_bdy=spec_bdy, sumflux=sumflux)
 
     def begin(self):
         """Asynchronous: [self-wrap refresh,] pack, then the interior cells (all of it with ``overlap=False``: nothing)."""
@@ -816,9 +682,6 @@ class ExternalGridStepper(_SumfluxOfStepper):
     def halo_unpack(self):
         self._call("halo_unpack")
 
-    def sync(self):
-        self._call("sync")
-
     def messages(self):
         """The handle's messages (``HaloMessageView``), sides in SIDE_ORDER; made once, the views stay valid until close()."""
         if self._messages is None:
@@ -826,44 +689,21 @@ class ExternalGridStepper(_SumfluxOfStepper):
             import torch
             ct = self._ct
             raw, n = (self._lib.HaloMessage * 4)(), ct.c_int()
-            self._lib.check(getattr(self.L, f"{self._HANDLE}_halo_messages")(self._h, raw, 4, ct.byref(n)))
+            self._lib.check(self._fn("halo_messages")(self._h, raw, 4, ct.byref(n)))
 
             def view(ptr, nbytes, on_host):
                 if on_host:
                     return np.frombuffer((ct.c_ubyte * nbytes).from_address(ptr), dtype=np.uint8)
-                return torch.as_tensor(_LibraryBytes(self, ptr, nbytes), device=torch.device("cuda", self.device_index))
+                return torch.as_tensor(self._lib.DeviceView(self, ptr, (nbytes,), "|u1"), device=torch.device("cuda", self.device_index))
 
             with self._dev():
                 self._messages = [HaloMessageView(m.side, m.peer, view(m.send, m.send_bytes, m.on_host),
                                                   view(m.recv, m.recv_bytes, m.on_host), bool(m.on_host)) for m in raw[:n.value]]
         return self._messages
 
-    def next_substep_inputs(self, seed: int, sweep: int, poison: bool = True):
-        """As NativeGridStepper.next_substep_inputs: new values in the exchanged fields, NaN in the halo rows and columns."""
-        _substep_inputs(self, self._dom, seed, sweep, self._halo_sides if poison else 0)
-
-    def halo_bytes_per_sweep(self) -> int:
-        return int(getattr(self.L, f"{self._HANDLE}_halo_bytes")(self._h))
-
-    def transport(self) -> str:
-        """'external', or 'none' for a patch without a neighbour."""
-        return getattr(self.L, f"{self._HANDLE}_transport")(self._h).decode()
-
     def close(self):
         self._messages = None
-        if self._h:
-            with self._dev():
-                getattr(self.L, f"{self._HANDLE}_destroy")(self._h)
-            self._h = self._ct.c_void_p()
-        if self._dom:
-            self.L.amt_domain_destroy(self._dom)
-            self._dom = self._ct.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
 
 class ExternalSlabStepper(ExternalGridStepper):

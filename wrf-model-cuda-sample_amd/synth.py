@@ -190,7 +190,7 @@ def _fill_args(b: Bounds, name: str, gdims):
     return (idim, kdim, jdim, b.ims, b.kms - 1, b.jms, gni + 2, gnk + 1, gnj + 2), r
 
 
-class NativeDomain(_lib.HandleDiag):
+class NativeDomain(_lib.ResidentHandle):
     """Owner of a resident handle made by ``amt_domain_create`` (the C-ABI a Fortran or C host calls, placement sampling
     included) whose 26 device arrays torch tensors VIEW through ``__cuda_array_interface__``: a Python caller then holds
     exactly the memory a native host would.  Destroyed with the last tensor that views it."""
@@ -200,67 +200,17 @@ class NativeDomain(_lib.HandleDiag):
         self.handle = ctypes.c_void_p()
         _lib.check(self.L.amt_domain_create(ctypes.byref(self.handle), itemsize, *config.as_ints(), *b.as_tuple()))
 
-    def step(self, n_sweeps: int = 1) -> None:
-        """``amt_domain_step``: asynchronous on the handle's stream."""
-        self._check(self.L.amt_domain_step(self.handle, int(n_sweeps)))
-
-    def step_timed(self, n_sweeps: int = 1) -> float:
-        ms = ctypes.c_float()
-        self._check(self.L.amt_domain_step_timed(self.handle, int(n_sweeps), ctypes.byref(ms)))
-        return float(ms.value)
-
-    def sync(self) -> None:
-        self._check(self.L.amt_domain_sync(self.handle))
-
     def placement_ms(self):
         """Sweep time (ms) on every allocation of the state that amt_domain_create timed; [] when it did not sample."""
         ms = (ctypes.c_float * 16)()
         n = int(self.L.amt_domain_placement(self.handle, ms, 16))
         return [round(float(ms[k]), 3) for k in range(n) if ms[k] > 0]
 
-    def set_cyclic(self, axes: int) -> None:
-        """``amt_domain_set_cyclic``: CYCLIC_X | CYCLIC_Y of api.py; every sweep of the handle's own stepping
-        (``amt_domain_step``) is then preceded by a refresh of the wrap cells.  0 = off."""
-        _lib.check(self.L.amt_domain_set_cyclic(self.handle, int(axes)))
-
-    def cyclic(self) -> int:
-        return int(self.L.amt_domain_cyclic(self.handle))
-
-    def cyclic_fill(self, axes: int) -> None:
-        """``amt_domain_cyclic_fill``: one refresh now, asynchronous on the handle's stream."""
-        _lib.check(self.L.amt_domain_cyclic_fill(self.handle, int(axes)))
-
-    def set_spec_bdy(self, on: bool = True) -> None:
-        """``amt_domain_set_spec_bdy``: every sweep of the handle's stepping is then followed by the boundary-zone update of a
-        specified / nested domain (header section 12).  False = off."""
-        _lib.check(self.L.amt_domain_set_spec_bdy(self.handle, int(bool(on))))
-
-    def spec_bdy(self) -> bool:
-        return bool(self.L.amt_domain_spec_bdy(self.handle))
-
-    def spec_bdy_update(self) -> None:
-        """``amt_domain_spec_bdy_update``: one update now, asynchronous on the handle's stream."""
-        _lib.check(self.L.amt_domain_spec_bdy_update(self.handle))
-
     def view(self, field_id: int, shape, typestr: str):
-        ptr = self.L.amt_domain_field_ptr(self.handle, field_id)
+        ptr = self.field_ptr(field_id)
         if not ptr:
             raise _lib.AmtError(_lib.ERR_INVALID_ARG, "amt_domain_field_ptr returned NULL")
-
-        class _View:                                   # keeps the owner alive for as long as a tensor views the array
-            pass
-        v = _View()
-        v.owner = self
-        v.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2, "strides": None}
-        return v
-
-    def __del__(self):
-        try:
-            if self.handle:
-                self.L.amt_domain_destroy(self.handle)
-                self.handle = ctypes.c_void_p()
-        except Exception:
-            pass
+        return _lib.DeviceView(self, ptr, shape, typestr)
 
 
 def make_patch(b: Bounds, config: GridConfig = GridConfig(), dtype=np.float64, seed: int = 12345,
