@@ -978,6 +978,94 @@ int amt_ensemble_sumflux_accumulate(amt_ensemble *e);
 int amt_ensemble_sumflux_state(const amt_ensemble *e, int *n, int *next_iteration);
 void *amt_ensemble_sumflux_ptr(amt_ensemble *e, int which);
 
+/* ------------------------------------------------------------------------
+ * (15) The bracket of a Runge-Kutta stage: small_step_prep and small_step_finish, on the device.  In solve_em every
+ *      Runge-Kutta stage opens its acoustic loop with small_step_prep, which turns the full fields into the perturbation form
+ *      advance_mu_t works on, and closes it with small_step_finish, which turns them back.  With these two calls
+ *      prep -> n x (sweep -> zone update (12) -> accumulation (14)) -> finish runs without a host round trip.  The reference has
+ *      no source for the two routines: the definition below is this library's contract, modelled on WRF's routines and
+ *      restricted to the arrays the library owns.  WRF's names: t = t_2, t_1 = t_save, ww_1 = ww1, mu = mu_2.  Arrays that
+ *      are not AMT_F_* fields: t_old (3-D; WRF's t_1: theta at the time level the RK step starts from), mu_old (2-D; WRF's
+ *      mu_1), mu_save (2-D), mub (2-D; base-state column mass, a pure input), h_diabatic (3-D; read by finish only, may be
+ *      NULL); `members` >= 1 patches are member-stacked as in (8).
+ *      Indices are Fortran-inclusive and global, on a tile its..ite, jts..jte with kts == 1 and kte == kde;
+ *      ihi = min(ite, ide-1), jhi = min(jte, jde-1); T is the arrays' type.  Every operation is rounded once in T, there is
+ *      no fused multiply-add, expressions associate exactly as written.  An assignment without arithmetic is a bit copy: NaN
+ *      payloads, signalling NaNs and -0.0 are kept.
+ *      PREP(rk_step), rk_step >= 1.  For every column i = its..ihi, j = jts..jhi, m = mu(i,j) as it was before the call:
+ *        rk_step == 1:  mu_old = m;  muts = mub + m;  mu_save = m;  mu = m - m;  mudf = +0.0
+ *                       (m - m is computed, not a stored zero: -0.0 gives +0.0, a NaN or +-Inf gives a NaN)
+ *        rk_step  > 1:  muts = mub + mu_old;  mu_save = m;  mu = mu_old - m;  mudf is not touched and may be NULL
+ *        cells k = kts..kte-1, x = t(i,k,j) before the call, s the NEW muts(i,j):
+ *                       at rk_step == 1  t_old = x (its old contents are not read and may be NaN);
+ *                       t_1 = x;  t = (s * t_old) - (mut * x)        two products, then one subtraction
+ *        cells k = kts..kte:  ww_1 = ww
+ *      FINISH(n, dts, h_diabatic), n = n_small_steps >= 1.  Over the same columns:
+ *        cells k = kts..kte-1:  t = ((t - ((dts * T(n)) * mut) * h_diabatic) + (t_1 * mut)) / muts      with h_diabatic,
+ *                               t = (t + (t_1 * mut)) / muts                                            without;
+ *                               an IEEE divide; for fp32 dts is rounded to float first, as the sweep does
+ *        cells k = kts..kte:    ww = ww + ww_1
+ *        columns:               mu = mu + mu_save
+ *      Always bit-unchanged, NaN payloads included: everything outside its..ihi x jts..jhi (column ide and row jde of a tile
+ *      that reaches them too), level kte of t, t_1 and t_old, every memory level outside kts..kte, every input.  No input
+ *      cell outside these ranges is read (halos may hold NaN), nothing outside the arrays is touched.  No atomics, no
+ *      workspace: the result is a function of the operands' contents alone.  Inputs may alias one another; an output
+ *      overlaps no other array of the call.  Prep is two launches in stream order (the 3-D pass reads the old mu, the 2-D
+ *      pass overwrites it), finish is one.
+ *      Reported before any device call, with or without a device, the arrays untouched:
+ *      AMT_ERR_INVALID_ARG: a NULL array other than h_diabatic, and mudf at rk_step > 1; members < 1; rk_step < 1; n < 1; an
+ *      output that overlaps another array.  AMT_ERR_PRECONDITION: the tile outside memory; kts != 1; kte != kde; kme < kte;
+ *      more than 65535 members.
+ *      NOT provided: the one-shot host-array calls of (1); u, v, w, ph and muus, muvs (they belong to advance_uv / advance_w);
+ *      the cells of t_1 OUTSIDE the tile that the sweep reads at i+-1, j+-1 (a host fills them as it does today: the cyclic
+ *      refresh (9), the steppers' halo exchange, which carries t_1, or its own boundary code); any coupling to the counter
+ *      of (14).
+ * ------------------------------------------------------------------------ */
+/* pointer level; asynchronous on hip_stream (NULL = the default stream) */
+int amt_stage_prep_device_f32(
+    void *hip_stream, int members, float *t, float *t_1, float *t_old, const float *ww, float *ww_1,
+    float *mu, float *mu_old, float *mu_save, float *muts, float *mudf, const float *mut, const float *mub, int rk_step,
+    int ids, int ide, int jds, int jde, int kde,
+    int ims, int ime, int jms, int jme, int kms, int kme,
+    int its, int ite, int jts, int jte, int kts, int kte);
+int amt_stage_prep_device_f64(
+    void *hip_stream, int members, double *t, double *t_1, double *t_old, const double *ww, double *ww_1,
+    double *mu, double *mu_old, double *mu_save, double *muts, double *mudf, const double *mut, const double *mub, int rk_step,
+    int ids, int ide, int jds, int jde, int kde,
+    int ims, int ime, int jms, int jme, int kms, int kme,
+    int its, int ite, int jts, int jte, int kts, int kte);
+int amt_stage_finish_device_f32(
+    void *hip_stream, int members, float *t, const float *t_1, float *ww, const float *ww_1,
+    float *mu, const float *mu_save, const float *muts, const float *mut, float dts, int n_small_steps, const float *h_diabatic,
+    int ids, int ide, int jds, int jde, int kde,
+    int ims, int ime, int jms, int jme, int kms, int kme,
+    int its, int ite, int jts, int jte, int kts, int kte);
+int amt_stage_finish_device_f64(
+    void *hip_stream, int members, double *t, const double *t_1, double *ww, const double *ww_1,
+    double *mu, const double *mu_save, const double *muts, const double *mut, double dts, int n_small_steps, const double *h_diabatic,
+    int ids, int ide, int jds, int jde, int kde,
+    int ims, int ime, int jms, int jme, int kms, int kme,
+    int its, int ite, int jts, int jte, int kts, int kte);
+/* on = 0: off (the default) and what the library allocated is freed; the handle's destroy frees it too.  on != 0 with t_old,
+ * mu_old, mu_save, mub all NULL: the library allocates the four arrays (t_old of a 3-D field's extents, the others of a 2-D
+ * field's, times the members of an ensemble; the host then fills mub once through amt_domain_stage_ptr); all four given: the
+ * caller's device arrays are used and never freed; a mix is AMT_ERR_INVALID_ARG.  (The library's own four, as
+ * amt_domain_stage_ptr returns them, may be handed back: nothing changes.)  A refusal changes nothing.  The setting is no
+ * per-sweep setting: amt_domain_step and amt_domain_tune_placement enqueue what they do without it.  A handle keeps it under
+ * amt_slab_* and amt_grid_*: prep and finish work on the rank's own tile, are issued on the domain handle between the stepper's
+ * step calls and are ordered by the domain's stream; nothing is exchanged for them. */
+int amt_domain_set_stage(amt_domain *d, int on, void *t_old, void *mu_old, void *mu_save, void *mub);
+void *amt_domain_stage_ptr(amt_domain *d, int which);             /* 0 t_old, 1 mu_old, 2 mu_save, 3 mub; NULL while off */
+/* prep in front of a stage's acoustic loop, finish (with the handle's dts; h_diabatic a caller-owned device array or NULL)
+ * behind it: asynchronous on the handle's stream (the caller's for a wrapped handle); AMT_ERR_PRECONDITION while off */
+int amt_domain_stage_prep(amt_domain *d, int rk_step);
+int amt_domain_stage_finish(amt_domain *d, int n_small_steps, const void *h_diabatic);
+/* the same for an ensemble: all members in one launch, member-stacked arrays */
+int amt_ensemble_set_stage(amt_ensemble *e, int on, void *t_old, void *mu_old, void *mu_save, void *mub);
+void *amt_ensemble_stage_ptr(amt_ensemble *e, int which);
+int amt_ensemble_stage_prep(amt_ensemble *e, int rk_step);
+int amt_ensemble_stage_finish(amt_ensemble *e, int n_small_steps, const void *h_diabatic);
+
 #ifdef __cplusplus
 }
 #endif

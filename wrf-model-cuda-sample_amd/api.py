@@ -182,6 +182,64 @@ def sumflux(ru_m, rv_m, ww_m, u, v, ww, u_1, v_1, ww_1, muu, muv, msfuy, msfvx_i
     _lib.check(status)
 
 
+def _stage_call(what, fn32, fn64, arrays, optional, sizes, members, stream, dtype, middle, bounds):
+    """The checks and the call ``stage_prep`` and ``stage_finish`` share: ``arrays`` are torch device tensors or device addresses
+    (then ``dtype`` names the element type), an entry of ``optional`` may be None."""
+    import torch
+    L = _lib.load_library()
+    tensors = [a for a in arrays if _is_torch(a)]
+    dt = dtype if dtype is not None else tensors[0].dtype if tensors else None
+    if dt not in (torch.float32, torch.float64):
+        raise TypeError(f"unsupported dtype {dt}")
+    for k, (a, n) in enumerate(zip(arrays, sizes)):
+        if a is None and k in optional:
+            continue
+        if _is_torch(a):
+            if not (a.is_cuda and a.dtype == dt and a.is_contiguous() and a.numel() == n * int(members)):
+                raise TypeError(f"{what} needs contiguous CUDA tensors of one dtype and of the memory extents")
+        elif not isinstance(a, int):
+            raise TypeError(f"{what} needs CUDA tensors or device addresses")
+    device = tensors[0].device if tensors else torch.device("cuda", torch.cuda.current_device())
+    if stream is None:
+        stream = torch.cuda.current_stream(device)
+    handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+    ptrs = [ctypes.c_void_p(None if a is None else a.data_ptr() if _is_torch(a) else a) for a in arrays]
+    with torch.cuda.device(device):
+        status = (fn32 if dt == torch.float32 else fn64)(ctypes.c_void_p(handle), int(members), *middle(ptrs),
+                                                          *[int(x) for x in bounds])
+    _lib.check(status)
+
+
+def stage_prep(t, t_1, t_old, ww, ww_1, mu, mu_old, mu_save, muts, mudf, mut, mub, rk_step,
+               ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,
+               its, ite, jts, jte, kts, kte, *, members=1, stream=None, dtype=None):
+    """small_step_prep of Runge-Kutta step ``rk_step`` (``amt_stage_prep_device_f32/_f64``, header section 15) on a patch's
+    (``members`` > 1: a member-stacked ensemble's) torch device tensors or device addresses (then with ``dtype``): the full
+    ``t``, ``mu`` become the perturbation form ``advance_mu_t`` works on, ``t_1``, ``ww_1``, ``mu_save`` (and at step 1 ``t_old``,
+    ``mu_old``) keep what finish needs, ``muts = mub + mu_old``.  ``mudf`` may be None at ``rk_step`` > 1.  Asynchronous on
+    ``stream`` (default: torch's current)."""
+    L = _lib.load_library()
+    n3, n2 = (jme - jms + 1) * (kme - kms + 1) * (ime - ims + 1), (jme - jms + 1) * (ime - ims + 1)
+    _stage_call("stage_prep", L.amt_stage_prep_device_f32, L.amt_stage_prep_device_f64,
+                (t, t_1, t_old, ww, ww_1, mu, mu_old, mu_save, muts, mudf, mut, mub), {9} if int(rk_step) > 1 else set(),
+                [n3] * 5 + [n2] * 7, members, stream, dtype, lambda p: p + [int(rk_step)],
+                (ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte))
+
+
+def stage_finish(t, t_1, ww, ww_1, mu, mu_save, muts, mut, dts, n_small_steps, h_diabatic,
+                 ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,
+                 its, ite, jts, jte, kts, kte, *, members=1, stream=None, dtype=None):
+    """small_step_finish behind an acoustic loop of ``n_small_steps`` sweeps (``amt_stage_finish_device_f32/_f64``, header
+    section 15): ``t = ((t - dts * n * mut * h_diabatic) + t_1 * mut) / muts`` (``h_diabatic`` may be None), ``ww += ww_1``,
+    ``mu += mu_save``.  Asynchronous on ``stream`` (default: torch's current)."""
+    L = _lib.load_library()
+    n3, n2 = (jme - jms + 1) * (kme - kms + 1) * (ime - ims + 1), (jme - jms + 1) * (ime - ims + 1)
+    _stage_call("stage_finish", L.amt_stage_finish_device_f32, L.amt_stage_finish_device_f64,
+                (t, t_1, ww, ww_1, mu, mu_save, muts, mut, h_diabatic), {8}, [n3] * 4 + [n2] * 4 + [n3], members, stream, dtype,
+                lambda p: p[:8] + [float(dts), int(n_small_steps), p[8]],
+                (ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte))
+
+
 def advance_mu_t(ww, ww_1, u, u_1, v, v_1, mu, mut, muave, muts, muu, muv, mudf, t, t_1,
                  t_ave, ft, mu_tend, rdx, rdy, dts, epssm, dnw, fnm, fnp, rdnw,
                  msfuy, msfvx_inv, msftx, msfty, config_flags,

@@ -20,6 +20,7 @@ void amt_handle_close(amt_domain *d)
     DeviceScope scope(d->device);
     amt_diag_release(d);
     amt_sumflux_release(d);
+    amt_stage_release(d);
     if (d->owns_fields)
         for (void *&q : d->field)
             if (q) { (void)hipFree(q); q = nullptr; }
@@ -422,6 +423,26 @@ int amt_handle_set_spec_bdy(const char *who, amt_domain *d, int members, int on)
 
 void *amt_handle_field_ptr(amt_domain *d, int field) { return field < 0 || field >= AMT_F_COUNT ? nullptr : d->field[field]; }
 
+// The bracket of a Runge-Kutta stage (header section 15): prep in front of a stage's acoustic loop, finish behind it, on the
+// handle's stream.  Not a per-sweep setting: the sweep sequence above does not know of it.  The refusals of amt_stage.hip come
+// back before the first device call; the device is made current behind them.
+int amt_handle_set_stage(const char *who, amt_domain *d, int members, int on, void *t_old, void *mu_old, void *mu_save, void *mub)
+{
+    return amt_stage_set_domain(who, d, members, on, t_old, mu_old, mu_save, mub);
+}
+
+void *amt_handle_stage_ptr(amt_domain *d, int which) { return which < 0 || which > 3 ? nullptr : d->stage_arr[which]; }
+
+int amt_handle_stage_prep(const char *who, amt_domain *d, int members, int rk_step)
+{
+    return amt_stage_prep_domain(who, d, members, rk_step);
+}
+
+int amt_handle_stage_finish(const char *who, amt_domain *d, int members, int n_small_steps, const void *h_diabatic)
+{
+    return amt_stage_finish_domain(who, d, members, n_small_steps, h_diabatic);
+}
+
 extern "C" int amt_domain_cyclic_fill(amt_domain *d, int axes)
 {
     return d ? amt_handle_cyclic_fill("amt_domain_cyclic_fill", d, 1, axes) : amt_null_domain();
@@ -440,6 +461,20 @@ extern "C" int amt_domain_set_spec_bdy(amt_domain *d, int on)
     return d ? amt_handle_set_spec_bdy("amt_domain_set_spec_bdy", d, 1, on) : amt_null_domain();
 }
 extern "C" int amt_domain_spec_bdy(const amt_domain *d) { return d ? d->spec_bdy : 0; }
+
+extern "C" int amt_domain_set_stage(amt_domain *d, int on, void *t_old, void *mu_old, void *mu_save, void *mub)
+{
+    return d ? amt_handle_set_stage("amt_domain_set_stage", d, 1, on, t_old, mu_old, mu_save, mub) : amt_null_domain();
+}
+extern "C" void *amt_domain_stage_ptr(amt_domain *d, int which) { return d ? amt_handle_stage_ptr(d, which) : nullptr; }
+extern "C" int amt_domain_stage_prep(amt_domain *d, int rk_step)
+{
+    return d ? amt_handle_stage_prep("amt_domain_stage_prep", d, 1, rk_step) : amt_null_domain();
+}
+extern "C" int amt_domain_stage_finish(amt_domain *d, int n_small_steps, const void *h_diabatic)
+{
+    return d ? amt_handle_stage_finish("amt_domain_stage_finish", d, 1, n_small_steps, h_diabatic) : amt_null_domain();
+}
 
 extern "C" int amt_domain_step(amt_domain *d, int n_sweeps)
 {

@@ -116,6 +116,20 @@ extern "C" int amt_ensemble_set_spec_bdy(amt_ensemble *e, int on)
 }
 extern "C" int amt_ensemble_spec_bdy(const amt_ensemble *e) { return e ? e->d.spec_bdy : 0; }
 
+extern "C" int amt_ensemble_set_stage(amt_ensemble *e, int on, void *t_old, void *mu_old, void *mu_save, void *mub)
+{
+    return e ? amt_handle_set_stage("amt_ensemble_set_stage", &e->d, e->members, on, t_old, mu_old, mu_save, mub) : amt_null_ensemble();
+}
+extern "C" void *amt_ensemble_stage_ptr(amt_ensemble *e, int which) { return e ? amt_handle_stage_ptr(&e->d, which) : nullptr; }
+extern "C" int amt_ensemble_stage_prep(amt_ensemble *e, int rk_step)
+{
+    return e ? amt_handle_stage_prep("amt_ensemble_stage_prep", &e->d, e->members, rk_step) : amt_null_ensemble();
+}
+extern "C" int amt_ensemble_stage_finish(amt_ensemble *e, int n_small_steps, const void *h_diabatic)
+{
+    return e ? amt_handle_stage_finish("amt_ensemble_stage_finish", &e->d, e->members, n_small_steps, h_diabatic) : amt_null_ensemble();
+}
+
 extern "C" int amt_ensemble_step(amt_ensemble *e, int n_sweeps)
 {
     if (!e || n_sweeps < 0) return amt_fail(AMT_ERR_INVALID_ARG, "bad step argument");

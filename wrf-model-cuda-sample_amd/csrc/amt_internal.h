@@ -194,6 +194,9 @@ struct amt_domain {
     int sumflux_next = 1;         // the iteration the next accumulation is, 1..sumflux_n
     void *sumflux_acc[3] = {};    // ru_m, rv_m, ww_m: one 3-D field's extents each (times the members of an ensemble)
     bool sumflux_owned = false;   // true: allocated by the library, freed with the setting or the handle
+    bool stage_on = false;        // the Runge-Kutta stage bracket is set up (amt_domain_set_stage)
+    void *stage_arr[4] = {};      // t_old (3-D), mu_old, mu_save, mub (2-D), times the members of an ensemble
+    bool stage_owned = false;     // true: allocated by the library, freed with the setting or the handle
     size_t count(int f) const
     {
         const size_t idim = ime - ims + 1, kdim = kme - kms + 1, jdim = jme - jms + 1;
@@ -269,6 +272,11 @@ int amt_handle_set_cyclic(const char *who, amt_domain *d, int members, int axes)
 int amt_handle_spec_bdy_update(const char *who, amt_domain *d, int members);
 int amt_handle_set_spec_bdy(const char *who, amt_domain *d, int members, int on);
 void *amt_handle_field_ptr(amt_domain *d, int field);
+// the Runge-Kutta stage bracket (header section 15): NOT part of the sweep sequence, a host calls them around its acoustic loop
+int amt_handle_set_stage(const char *who, amt_domain *d, int members, int on, void *t_old, void *mu_old, void *mu_save, void *mub);
+void *amt_handle_stage_ptr(amt_domain *d, int which);
+int amt_handle_stage_prep(const char *who, amt_domain *d, int members, int rk_step);
+int amt_handle_stage_finish(const char *who, amt_domain *d, int members, int n_small_steps, const void *h_diabatic);
 int amt_handle_copy(amt_domain *d, void *dev, void *host, size_t bytes, bool up);
 int amt_handle_fill(amt_domain *d, int members, uint64_t field_mask, uint64_t seed,
                     long gi0, long gk0, long gj0, long gidim, long gkdim, long gjdim);
@@ -300,6 +308,20 @@ int amt_bdy_check_domain(const char *who, const amt_domain *d, int members);
 int amt_sumflux_accumulate_domain(const char *who, amt_domain *d, int members);
 int amt_sumflux_set_domain(const char *who, amt_domain *d, int members, int n, void *ru_m, void *rv_m, void *ww_m);
 void amt_sumflux_release(amt_domain *d);
+
+// ---------------------------------------------------------------------------
+// the bracket of a Runge-Kutta stage (amt_stage.hip, header section 15): small_step_prep and small_step_finish of `members`
+// member-stacked patches of the domain's shape on the domain's stream.  Nothing of the sweep sequence calls these.
+//   amt_stage_prep_domain / amt_stage_finish_domain: AMT_ERR_PRECONDITION while the setting is off; finish uses the domain's dts
+//   amt_stage_set_domain:                            amt_*_set_stage (on = 0: off); a refusal changes nothing
+//   amt_stage_release:                               turns the setting off and frees what the library allocated
+// ---------------------------------------------------------------------------
+#pragma GCC visibility push(hidden)
+int amt_stage_prep_domain(const char *who, amt_domain *d, int members, int rk_step);
+int amt_stage_finish_domain(const char *who, amt_domain *d, int members, int n_small_steps, const void *h_diabatic);
+int amt_stage_set_domain(const char *who, amt_domain *d, int members, int on, void *t_old, void *mu_old, void *mu_save, void *mub);
+void amt_stage_release(amt_domain *d);
+#pragma GCC visibility pop
 
 // ---------------------------------------------------------------------------
 // field statistics, comparison and the non-finite guard (amt_diag.hip, header section 10).  The steppers call these only

@@ -1,0 +1,531 @@
+// amt_stage.hip -- the bracket of a Runge-Kutta stage on the device (include/amt_advance_mu_t.h section 15, DESIGN.md
+// section 7.8).  In WRF's solve_em every Runge-Kutta stage opens its acoustic loop with small_step_prep, which turns the full
+// fields into the perturbation form advance_mu_t works on, and closes it with small_step_finish, which turns them back.  For
+// the arrays this library owns (t = t_2, t_1 = t_save, ww_1 = ww1, mu = mu_2; t_old = WRF's t_1, mu_old = WRF's mu_1):
+//   prep, rk_step == 1:  mu_old = m; muts = mub + m; mu_save = m; mu = m - m; mudf = 0          (m the old mu)
+//         rk_step  > 1:  muts = mub + mu_old; mu_save = m; mu = mu_old - m
+//         cells:         [t_old = x;]  t_1 = x;  t = (s * t_old) - (mut * x);   ww_1 = ww        (x the old t, s the NEW muts)
+//   finish:              t = ((t - ((dts * n) * mut) * h_diabatic) + (t_1 * mut)) / muts    or   t = (t + (t_1 * mut)) / muts
+//                        ww = ww + ww_1;  mu = mu + mu_save
+// over the columns its..min(ite, ide-1), jts..min(jte, jde-1), t on levels kts..kte-1 and ww on kts..kte; every operation
+// rounded once in the arrays' type (the library is built with -ffp-contract=off), copies are bit copies.
+// The 3-D pass of prep needs the OLD mu and works out s = mub + m itself -- the same rounding as the stored muts --, while the
+// 2-D pass overwrites mu, mu_old, mu_save and muts: in one launch the two would race between workgroups.  So prep is TWO
+// launches in stream order, the 3-D pass first (it never reads the stored muts), and finish, which has no such dependency, is
+// ONE.  Separate streaming passes around the acoustic loop: the march kernel is not touched.
+#include "amt_internal.h"
+
+namespace {
+// A job works on a box of nk * nj runs of `ni` contiguous elements, run r = (k, j) = (r % nk, r / nk) of member m starting at
+// element m * mstride3 + j * jstride3 + k * idim + first3 of every 3-D array (they have one layout) and at
+// m * mstride2 + j * idim + first2 of every 2-D array.  Job t covers the levels kts..kte-1 (nk - 1 of them), job ww all nk;
+// the 2-D job is one run per row j.
+template <typename T>
+struct AmtStageJobs {
+    T *t, *t_1, *t_old, *ww, *ww_1;
+    T *mu, *mu_old, *mu_save, *muts, *mudf;
+    const T *mut, *mub, *h;
+    int ni, nk, nj;
+    long idim, jstride3, mstride3, mstride2, first3, first2;
+    T c;                                                           // finish: dts * T(n_small_steps), rounded once in T
+    int first, with_h;                                             // rk_step == 1; h_diabatic given
+};
+
+template <typename T> struct AmtStageVec;
+template <> struct AmtStageVec<float> { typedef float type __attribute__((ext_vector_type(4))); };
+template <> struct AmtStageVec<double> { typedef double type __attribute__((ext_vector_type(2))); };
+
+// Work item e of a 3-D job: one 16-byte chunk of a run, counted from the run's first element (the run's last chunk may be
+// short); lanes run along (chunk, k, j), along i first, so that every stream of a wave is coalesced.  Offsets are 64-bit.
+template <int kPer>
+__device__ __forceinline__ void amt_stage_chunk(long e, long chunks, long nk, long ni, bool narrow, long idim, long jstride3,
+                                                long &at3, long &at2, int &cnt)
+{
+    long r, j;
+    if (narrow) {                                                  // wave-uniform: 32-bit divisions where they suffice
+        r = (long)((unsigned)e / (unsigned)chunks);
+        j = (long)((unsigned)r / (unsigned)nk);
+    } else {
+        r = e / chunks;
+        j = r / nk;
+    }
+    const long k = r - j * nk;
+    const long i0 = (e - r * chunks) * kPer;
+    at3 = j * jstride3 + k * idim + i0;
+    at2 = j * idim + i0;
+    const long left = ni - i0;
+    cnt = left < kPer ? (int)left : kPer;
+}
+
+// The common 16-byte phase of a job's 3-D streams behind the member offset (wave-uniform), or -1 where they differ.  A chunk at
+// element offset `at` has ALL its 3-D addresses on a 16-byte boundary exactly when the phase is common and phase + at * sizeof(T)
+// is a multiple of 16.
+__device__ __forceinline__ int amt_stage_phase(const void *a, const void *b, const void *c)
+{
+    const int pa = (int)(reinterpret_cast<uintptr_t>(a) & 15), pb = (int)(reinterpret_cast<uintptr_t>(b) & 15), pc = (int)(reinterpret_cast<uintptr_t>(c) & 15);
+    return pa == pb && pa == pc ? pa : -1;
+}
+template <typename T>
+__device__ __forceinline__ bool amt_stage_aligned(int phase, long at)
+{
+    return phase >= 0 && (((long)phase + at * (long)sizeof(T)) & 15) == 0;
+}
+
+// what prep stores into t: two products, then one subtraction
+template <typename T>
+__device__ __forceinline__ T amt_stage_prep_t(T s, T told, T mut, T x)
+{
+    const T a = s * told, b = mut * x;
+    return a - b;
+}
+
+// what finish stores into t; c = dts * T(n)
+template <typename T>
+__device__ __forceinline__ T amt_stage_finish_t(bool with_h, T x, T c, T mut, T h, T t1, T muts)
+{
+    T acc = x;
+    if (with_h) {
+        const T a = c * mut;
+        const T b = a * h;
+        acc = x - b;
+    }
+    const T e = t1 * mut;
+    const T f = acc + e;
+    return f / muts;
+}
+
+// The 3-D pass of prep.  Grid (blocks, 2 jobs, members): job 0 is t (reads mu or mu_old, mub, mut; never muts), job 1 the copy
+// ww_1 = ww.  A whole chunk moves as ONE 16-byte access per 3-D stream where all the 3-D addresses it touches lie on a 16-byte
+// boundary (decided per chunk from the streams' common phase behind the member offset); a run's short last chunk and every other chunk go element by
+// element, with the same arithmetic.  The 2-D operands are loaded element by element.  256 threads, no LDS.
+template <typename T>
+__global__ __launch_bounds__(256) void amt_stage_prep3_kernel(AmtStageJobs<T> jobs)
+{
+    typedef typename AmtStageVec<T>::type V;
+    constexpr int kPer = 16 / (int)sizeof(T);
+    const int q = blockIdx.y;
+    const long moff3 = (long)blockIdx.z * jobs.mstride3 + jobs.first3, moff2 = (long)blockIdx.z * jobs.mstride2 + jobs.first2;
+    const bool first = jobs.first != 0;
+    const long ni = jobs.ni, nk = q == 0 ? jobs.nk - 1 : jobs.nk;
+    const long chunks = (ni + kPer - 1) / kPer;
+    const long total = nk * (long)jobs.nj * chunks;
+    const bool narrow = total <= 0x7fffffffL;
+    if (q == 1) {                                                  // ww_1 = ww
+        const T *ww = jobs.ww + moff3;
+        T *ww_1 = jobs.ww_1 + moff3;
+        const int phase = amt_stage_phase(ww, ww_1, ww);
+        for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+            long at3, at2;
+            int cnt;
+            amt_stage_chunk<kPer>(e, chunks, nk, ni, narrow, jobs.idim, jobs.jstride3, at3, at2, cnt);
+            if (cnt == kPer && amt_stage_aligned<T>(phase, at3)) {
+                *reinterpret_cast<V *>(ww_1 + at3) = *reinterpret_cast<const V *>(ww + at3);
+            } else {
+                for (int i = 0; i < cnt; ++i) ww_1[at3 + i] = ww[at3 + i];
+            }
+        }
+        return;
+    }
+    const T *m2 = (first ? jobs.mu : jobs.mu_old) + moff2, *mub = jobs.mub + moff2, *mut = jobs.mut + moff2;
+    T *t = jobs.t + moff3, *t_1 = jobs.t_1 + moff3, *t_old = jobs.t_old + moff3;
+    const int phase = amt_stage_phase(t, t_1, t_old);
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        long at3, at2;
+        int cnt;
+        amt_stage_chunk<kPer>(e, chunks, nk, ni, narrow, jobs.idim, jobs.jstride3, at3, at2, cnt);
+        if (cnt == kPer && amt_stage_aligned<T>(phase, at3)) {
+            const V x = *reinterpret_cast<const V *>(t + at3);
+            V old = x, out;
+            if (!first) old = *reinterpret_cast<const V *>(t_old + at3);
+            for (int i = 0; i < kPer; ++i) {
+                const T s = mub[at2 + i] + m2[at2 + i];
+                out[i] = amt_stage_prep_t<T>(s, old[i], mut[at2 + i], x[i]);
+            }
+            if (first) *reinterpret_cast<V *>(t_old + at3) = x;
+            *reinterpret_cast<V *>(t_1 + at3) = x;
+            *reinterpret_cast<V *>(t + at3) = out;
+        } else {
+            for (int i = 0; i < cnt; ++i) {
+                const T x = t[at3 + i];
+                const T old = first ? x : t_old[at3 + i];
+                const T s = mub[at2 + i] + m2[at2 + i];
+                const T out = amt_stage_prep_t<T>(s, old, mut[at2 + i], x);
+                if (first) t_old[at3 + i] = x;
+                t_1[at3 + i] = x;
+                t[at3 + i] = out;
+            }
+        }
+    }
+}
+
+// The 2-D pass of prep, behind the 3-D pass in stream order.  Grid (blocks, 1, members), one column per lane, lanes along i.
+template <typename T>
+__global__ __launch_bounds__(256) void amt_stage_prep2_kernel(AmtStageJobs<T> jobs)
+{
+    const long moff2 = (long)blockIdx.z * jobs.mstride2 + jobs.first2;
+    const bool first = jobs.first != 0;
+    const long ni = jobs.ni, total = ni * (long)jobs.nj;
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const long j = e / ni;
+        const long at = moff2 + j * jobs.idim + (e - j * ni);
+        const T m = jobs.mu[at];
+        if (first) {
+            jobs.mu_old[at] = m;
+            jobs.muts[at] = jobs.mub[at] + m;
+            jobs.mu_save[at] = m;
+            jobs.mu[at] = m - m;
+            jobs.mudf[at] = T(0);
+        } else {
+            const T old = jobs.mu_old[at];
+            jobs.muts[at] = jobs.mub[at] + old;
+            jobs.mu_save[at] = m;
+            jobs.mu[at] = old - m;
+        }
+    }
+}
+
+// finish.  Grid (blocks, 3 jobs, members): job 0 is t, job 1 ww = ww + ww_1 (chunks as in the 3-D pass of prep), job 2
+// mu = mu + mu_save (one column per lane).  No job reads what another writes.
+template <typename T>
+__global__ __launch_bounds__(256) void amt_stage_finish_kernel(AmtStageJobs<T> jobs)
+{
+    typedef typename AmtStageVec<T>::type V;
+    constexpr int kPer = 16 / (int)sizeof(T);
+    const int q = blockIdx.y;
+    const long moff3 = (long)blockIdx.z * jobs.mstride3 + jobs.first3, moff2 = (long)blockIdx.z * jobs.mstride2 + jobs.first2;
+    const long ni = jobs.ni;
+    if (q == 2) {
+        const long total = ni * (long)jobs.nj;
+        for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+            const long j = e / ni;
+            const long at = moff2 + j * jobs.idim + (e - j * ni);
+            jobs.mu[at] = jobs.mu[at] + jobs.mu_save[at];
+        }
+        return;
+    }
+    const bool with_h = jobs.with_h != 0;
+    const T c = jobs.c;
+    const long nk = q == 0 ? jobs.nk - 1 : jobs.nk;
+    const long chunks = (ni + kPer - 1) / kPer;
+    const long total = nk * (long)jobs.nj * chunks;
+    const bool narrow = total <= 0x7fffffffL;
+    if (q == 1) {                                                  // ww = ww + ww_1
+        T *ww = jobs.ww + moff3;
+        const T *ww_1 = jobs.ww_1 + moff3;
+        const int phase = amt_stage_phase(ww, ww_1, ww);
+        for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+            long at3, at2;
+            int cnt;
+            amt_stage_chunk<kPer>(e, chunks, nk, ni, narrow, jobs.idim, jobs.jstride3, at3, at2, cnt);
+            if (cnt == kPer && amt_stage_aligned<T>(phase, at3)) {
+                V a = *reinterpret_cast<const V *>(ww + at3);
+                const V b = *reinterpret_cast<const V *>(ww_1 + at3);
+                for (int i = 0; i < kPer; ++i) a[i] = a[i] + b[i];
+                *reinterpret_cast<V *>(ww + at3) = a;
+            } else {
+                for (int i = 0; i < cnt; ++i) ww[at3 + i] = ww[at3 + i] + ww_1[at3 + i];
+            }
+        }
+        return;
+    }
+    const T *mut = jobs.mut + moff2, *muts = jobs.muts + moff2;
+    T *t = jobs.t + moff3;
+    const T *t_1 = jobs.t_1 + moff3, *h = with_h ? jobs.h + moff3 : t_1;
+    const int phase = amt_stage_phase(t, t_1, h);
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        long at3, at2;
+        int cnt;
+        amt_stage_chunk<kPer>(e, chunks, nk, ni, narrow, jobs.idim, jobs.jstride3, at3, at2, cnt);
+        if (cnt == kPer && amt_stage_aligned<T>(phase, at3)) {
+            V x = *reinterpret_cast<const V *>(t + at3);
+            const V t1 = *reinterpret_cast<const V *>(t_1 + at3);
+            V hv = t1;
+            if (with_h) hv = *reinterpret_cast<const V *>(h + at3);
+            for (int i = 0; i < kPer; ++i) x[i] = amt_stage_finish_t<T>(with_h, x[i], c, mut[at2 + i], hv[i], t1[i], muts[at2 + i]);
+            *reinterpret_cast<V *>(t + at3) = x;
+        } else {
+            for (int i = 0; i < cnt; ++i)
+                t[at3 + i] = amt_stage_finish_t<T>(with_h, t[at3 + i], c, mut[at2 + i], with_h ? h[at3 + i] : T(0), t_1[at3 + i], muts[at2 + i]);
+        }
+    }
+}
+
+// One array of a call, for the checks: outputs may overlap nothing, inputs may alias one another.
+struct StageArray {
+    const void *p;
+    bool three_d, output, optional;
+};
+
+// Argument and precondition checks: host arithmetic only.  *empty: the range holds no column (nothing to do).
+int stage_check(const char *who, const amt_domain &s, int members, const StageArray *arr, int narr, const char *count_name, int count,
+                bool *empty)
+{
+    *empty = false;
+    for (int k = 0; k < narr; ++k)
+        if (!arr[k].p && !arr[k].optional) return amt_fail(AMT_ERR_INVALID_ARG, "%s: null array pointer", who);
+    if (members < 1) return amt_fail(AMT_ERR_INVALID_ARG, "%s: members = %d: an ensemble has at least one member", who, members);
+    if (count < 1) return amt_fail(AMT_ERR_INVALID_ARG, "%s: %s = %d: at least 1", who, count_name, count);
+    if (s.ime < s.ims || s.jme < s.jms || s.kme < s.kms) return amt_fail(AMT_ERR_PRECONDITION, "%s: empty memory extents", who);
+    const size_t idim = s.ime - s.ims + 1, kdim = s.kme - s.kms + 1, jdim = s.jme - s.jms + 1;
+    const size_t b3 = idim * kdim * jdim * (size_t)members * (size_t)s.dtype_bytes, b2 = idim * jdim * (size_t)members * (size_t)s.dtype_bytes;
+    for (int k = 0; k < narr; ++k) {
+        if (!arr[k].p) continue;
+        const uintptr_t p0 = reinterpret_cast<uintptr_t>(arr[k].p), pb = arr[k].three_d ? b3 : b2;
+        for (int m = k + 1; m < narr; ++m) {
+            if (!arr[m].p || !(arr[k].output || arr[m].output)) continue;
+            const uintptr_t r0 = reinterpret_cast<uintptr_t>(arr[m].p), rb = arr[m].three_d ? b3 : b2;
+            if (p0 < r0 + rb && r0 < p0 + pb) return amt_fail(AMT_ERR_INVALID_ARG, "%s: an output array overlaps another array of the call", who);
+        }
+    }
+    if (s.kts != 1) return amt_fail(AMT_ERR_PRECONDITION, "%s: kts = %d, the library needs kts == 1", who, s.kts);
+    if (s.kte != s.kde) return amt_fail(AMT_ERR_PRECONDITION, "%s: kte = %d is not kde = %d", who, s.kte, s.kde);
+    if (s.kme < s.kte || s.kms > s.kts) return amt_fail(AMT_ERR_PRECONDITION, "%s: levels kts:kte = %d:%d are not inside memory kms:kme = %d:%d", who, s.kts, s.kte, s.kms, s.kme);
+    if (s.ite < s.its || s.jte < s.jts || s.kte < s.kts) { *empty = true; return AMT_OK; }
+    if (s.its < s.ims || s.ite > s.ime || s.jts < s.jms || s.jte > s.jme)
+        return amt_fail(AMT_ERR_PRECONDITION, "%s: the tile %d:%d, %d:%d is not inside memory %d:%d, %d:%d", who,
+                        s.its, s.ite, s.jts, s.jte, s.ims, s.ime, s.jms, s.jme);
+    if (members > 65535) return amt_fail(AMT_ERR_PRECONDITION, "%s: %d members: one launch covers at most 65535", who, members);
+    const int ihi = s.ite < s.ide - 1 ? s.ite : s.ide - 1, jhi = s.jte < s.jde - 1 ? s.jte : s.jde - 1;
+    if (ihi < s.its || jhi < s.jts) *empty = true;
+    return AMT_OK;
+}
+
+struct StagePrepArrays {
+    void *t, *t_1, *t_old;
+    const void *ww;
+    void *ww_1, *mu, *mu_old, *mu_save, *muts, *mudf;
+    const void *mut, *mub;
+};
+struct StageFinishArrays {
+    void *t;
+    const void *t_1;
+    void *ww;
+    const void *ww_1;
+    void *mu;
+    const void *mu_save, *muts, *mut, *h;
+};
+
+int stage_prep_check(const char *who, const amt_domain &d, int members, const StagePrepArrays &a, int rk_step, bool *empty)
+{
+    const bool first = rk_step == 1;
+    // mudf at rk_step > 1 is neither read nor written: it takes no part in the checks
+    const StageArray arr[12] = {{a.t, true, true, false}, {a.t_1, true, true, false}, {a.t_old, true, first, false},
+                                {a.ww, true, false, false}, {a.ww_1, true, true, false}, {a.mu, false, true, false},
+                                {a.mu_old, false, first, false}, {a.mu_save, false, true, false}, {a.muts, false, true, false},
+                                {first ? a.mudf : nullptr, false, true, !first}, {a.mut, false, false, false}, {a.mub, false, false, false}};
+    return stage_check(who, d, members, arr, 12, "rk_step", rk_step, empty);
+}
+
+int stage_finish_check(const char *who, const amt_domain &d, int members, const StageFinishArrays &a, int n, bool *empty)
+{
+    const StageArray arr[9] = {{a.t, true, true, false}, {a.t_1, true, false, false}, {a.ww, true, true, false},
+                               {a.ww_1, true, false, false}, {a.mu, false, true, false}, {a.mu_save, false, false, false},
+                               {a.muts, false, false, false}, {a.mut, false, false, false}, {a.h, true, false, true}};
+    return stage_check(who, d, members, arr, 9, "n_small_steps", n, empty);
+}
+
+template <typename T>
+void stage_box(const amt_domain &d, AmtStageJobs<T> &jobs)
+{
+    const long idim = d.ime - d.ims + 1, kdim = d.kme - d.kms + 1, jdim = d.jme - d.jms + 1;
+    jobs.ni = (d.ite < d.ide - 1 ? d.ite : d.ide - 1) - d.its + 1;
+    jobs.nk = d.kte - d.kts + 1;
+    jobs.nj = (d.jte < d.jde - 1 ? d.jte : d.jde - 1) - d.jts + 1;
+    jobs.idim = idim; jobs.jstride3 = kdim * idim; jobs.mstride3 = idim * kdim * jdim; jobs.mstride2 = idim * jdim;
+    jobs.first3 = ((long)(d.jts - d.jms) * kdim + (d.kts - d.kms)) * idim + (d.its - d.ims);
+    jobs.first2 = (long)(d.jts - d.jms) * idim + (d.its - d.ims);
+}
+
+// blocks of 256 threads for `total` work items: as many as amt_sumflux.hip uses at the most
+unsigned stage_blocks(long total)
+{
+    long blocks = (total + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    return (unsigned)(blocks < 1 ? 1 : blocks);
+}
+
+template <typename T>
+int stage_prep_launch(const amt_domain &d, int members, const StagePrepArrays &a, int rk_step)
+{
+    AmtStageJobs<T> jobs{};
+    jobs.t = static_cast<T *>(a.t); jobs.t_1 = static_cast<T *>(a.t_1); jobs.t_old = static_cast<T *>(a.t_old);
+    jobs.ww = static_cast<T *>(const_cast<void *>(a.ww)); jobs.ww_1 = static_cast<T *>(a.ww_1);
+    jobs.mu = static_cast<T *>(a.mu); jobs.mu_old = static_cast<T *>(a.mu_old); jobs.mu_save = static_cast<T *>(a.mu_save);
+    jobs.muts = static_cast<T *>(a.muts); jobs.mudf = static_cast<T *>(a.mudf);
+    jobs.mut = static_cast<const T *>(a.mut); jobs.mub = static_cast<const T *>(a.mub);
+    jobs.first = rk_step == 1;
+    stage_box<T>(d, jobs);
+    constexpr long per = 16 / (long)sizeof(T);
+    const long most = (long)jobs.nk * jobs.nj * ((jobs.ni + per - 1) / per);               // job ww, the larger of the two
+    hipLaunchKernelGGL(amt_stage_prep3_kernel<T>, dim3(stage_blocks(most), 2, (unsigned)members), dim3(256), 0, d.stream, jobs);
+    AMT_HIP(hipGetLastError());
+    hipLaunchKernelGGL(amt_stage_prep2_kernel<T>, dim3(stage_blocks((long)jobs.ni * jobs.nj), 1, (unsigned)members), dim3(256), 0, d.stream, jobs);
+    AMT_HIP(hipGetLastError());
+    return AMT_OK;
+}
+
+template <typename T>
+int stage_finish_launch(const amt_domain &d, int members, const StageFinishArrays &a, double dts, int n)
+{
+    AmtStageJobs<T> jobs{};
+    jobs.t = static_cast<T *>(a.t); jobs.t_1 = static_cast<T *>(const_cast<void *>(a.t_1));
+    jobs.ww = static_cast<T *>(a.ww); jobs.ww_1 = static_cast<T *>(const_cast<void *>(a.ww_1));
+    jobs.mu = static_cast<T *>(a.mu); jobs.mu_save = static_cast<T *>(const_cast<void *>(a.mu_save));
+    jobs.muts = static_cast<T *>(const_cast<void *>(a.muts));
+    jobs.mut = static_cast<const T *>(a.mut); jobs.h = static_cast<const T *>(a.h);
+    jobs.with_h = a.h != nullptr;
+    const T dts_t = (T)dts, n_t = (T)n;
+    jobs.c = dts_t * n_t;
+    stage_box<T>(d, jobs);
+    constexpr long per = 16 / (long)sizeof(T);
+    const long most = (long)jobs.nk * jobs.nj * ((jobs.ni + per - 1) / per);
+    hipLaunchKernelGGL(amt_stage_finish_kernel<T>, dim3(stage_blocks(most), 3, (unsigned)members), dim3(256), 0, d.stream, jobs);
+    AMT_HIP(hipGetLastError());
+    return AMT_OK;
+}
+
+// with_device_check: the pointer-level calls, which may be the first HIP call of a process, report a missing device
+// themselves -- behind the argument errors, which need none
+int stage_device_present()
+{
+    int ndev = 0;
+    AMT_HIP(hipGetDeviceCount(&ndev));
+    if (ndev < 1) return amt_fail(AMT_ERR_NO_DEVICE, "no HIP device visible");
+    return AMT_OK;
+}
+
+// the pointer-level calls run on the caller's current device
+int stage_current_device()
+{
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    return dev;
+}
+
+int stage_prep_run(const char *who, const amt_domain &d, int members, const StagePrepArrays &a, int rk_step, bool with_device_check)
+{
+    bool empty = false;
+    int rc = stage_prep_check(who, d, members, a, rk_step, &empty);
+    if (rc != AMT_OK || empty) return rc;
+    if (with_device_check && (rc = stage_device_present()) != AMT_OK) return rc;
+    DeviceScope scope(with_device_check ? stage_current_device() : d.device);          // a handle's launches go to its device
+    return d.dtype_bytes == 8 ? stage_prep_launch<double>(d, members, a, rk_step) : stage_prep_launch<float>(d, members, a, rk_step);
+}
+
+int stage_finish_run(const char *who, const amt_domain &d, int members, const StageFinishArrays &a, double dts, int n, bool with_device_check)
+{
+    bool empty = false;
+    int rc = stage_finish_check(who, d, members, a, n, &empty);
+    if (rc != AMT_OK || empty) return rc;
+    if (with_device_check && (rc = stage_device_present()) != AMT_OK) return rc;
+    DeviceScope scope(with_device_check ? stage_current_device() : d.device);
+    return d.dtype_bytes == 8 ? stage_finish_launch<double>(d, members, a, dts, n) : stage_finish_launch<float>(d, members, a, dts, n);
+}
+
+StagePrepArrays stage_prep_of_domain(const amt_domain *d)
+{
+    return StagePrepArrays{d->field[AMT_F_T], d->field[AMT_F_T_1], d->stage_arr[0], d->field[AMT_F_WW], d->field[AMT_F_WW_1],
+                           d->field[AMT_F_MU], d->stage_arr[1], d->stage_arr[2], d->field[AMT_F_MUTS], d->field[AMT_F_MUDF],
+                           d->field[AMT_F_MUT], d->stage_arr[3]};
+}
+}  // namespace
+
+// ---- what the handles call (amt_handle_stage_* of amt_domain.hip) ---------------------------------------------------------
+int amt_stage_prep_domain(const char *who, amt_domain *d, int members, int rk_step)
+{
+    if (!d->stage_on) return amt_fail(AMT_ERR_PRECONDITION, "%s: the stage bracket is off (amt_*_set_stage)", who);
+    return stage_prep_run(who, *d, members, stage_prep_of_domain(d), rk_step, false);
+}
+
+int amt_stage_finish_domain(const char *who, amt_domain *d, int members, int n_small_steps, const void *h_diabatic)
+{
+    if (!d->stage_on) return amt_fail(AMT_ERR_PRECONDITION, "%s: the stage bracket is off (amt_*_set_stage)", who);
+    const StageFinishArrays a{d->field[AMT_F_T], d->field[AMT_F_T_1], d->field[AMT_F_WW], d->field[AMT_F_WW_1], d->field[AMT_F_MU],
+                              d->stage_arr[2], d->field[AMT_F_MUTS], d->field[AMT_F_MUT], h_diabatic};
+    return stage_finish_run(who, *d, members, a, d->dts, n_small_steps, false);
+}
+
+void amt_stage_release(amt_domain *d)
+{
+    for (void *&q : d->stage_arr) {
+        if (q && d->stage_owned) (void)hipFree(q);
+        q = nullptr;
+    }
+    d->stage_on = false;
+    d->stage_owned = false;
+}
+
+// amt_*_set_stage.  A refusal changes nothing.
+int amt_stage_set_domain(const char *who, amt_domain *d, int members, int on, void *t_old, void *mu_old, void *mu_save, void *mub)
+{
+    if (!on) {
+        DeviceScope scope(d->device);
+        amt_stage_release(d);
+        return AMT_OK;
+    }
+    void *arr[4] = {t_old, mu_old, mu_save, mub};
+    const int given = (t_old != nullptr) + (mu_old != nullptr) + (mu_save != nullptr) + (mub != nullptr);
+    if (given != 0 && given != 4)
+        return amt_fail(AMT_ERR_INVALID_ARG, "%s: give all four arrays or none (the library then allocates them)", who);
+    // the library's own arrays handed back (amt_*_stage_ptr): they stay the library's; some of them among the caller's would be
+    // freed under the caller
+    const bool same = given == 4 && d->stage_owned && memcmp(arr, d->stage_arr, sizeof arr) == 0;
+    if (same) return AMT_OK;
+    if (given == 4 && d->stage_owned)
+        for (void *mine : d->stage_arr)
+            for (void *theirs : arr)
+                if (mine == theirs) return amt_fail(AMT_ERR_INVALID_ARG, "%s: an array the library allocated, mixed with others", who);
+    if (given == 4) {
+        amt_domain probe = *d;                                     // the checks against the caller's arrays, nothing enqueued
+        memcpy(probe.stage_arr, arr, sizeof arr);
+        bool empty = false;
+        const int rc = stage_prep_check(who, probe, members, stage_prep_of_domain(&probe), 1, &empty);
+        if (rc) return rc;
+    } else {
+        if (members > 65535) return amt_fail(AMT_ERR_PRECONDITION, "%s: %d members: one launch covers at most 65535", who, members);
+        if (d->kts != 1 || d->kte != d->kde || d->kme < d->kte || d->kms > d->kts || d->its < d->ims || d->ite > d->ime || d->jts < d->jms || d->jte > d->jme)
+            return amt_fail(AMT_ERR_PRECONDITION, "%s: the handle's tile does not admit the stage bracket (kts == 1, kte == kde, tile inside memory)", who);
+    }
+    DeviceScope scope(d->device);                                  // behind every refusal but a failed allocation
+    if (given == 0) {
+        for (int k = 0; k < 4; ++k) {
+            const size_t bytes = d->count(k == 0 ? AMT_F_T : AMT_F_MU) * (size_t)members * (size_t)d->dtype_bytes;
+            arr[k] = nullptr;
+            if (hipMalloc(&arr[k], bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                for (int m = 0; m < k; ++m) (void)hipFree(arr[m]);
+                return amt_fail(AMT_ERR_ALLOC, "%s: no room for an array of %zu bytes", who, bytes);
+            }
+        }
+    }
+    amt_stage_release(d);
+    memcpy(d->stage_arr, arr, sizeof arr);
+    d->stage_owned = given == 0;
+    d->stage_on = true;
+    return AMT_OK;
+}
+
+// ---- pointer level -------------------------------------------------------------------------------------------------------
+#define AMT_STAGE_BOUNDS_SIG                                                                                    \
+    int ids, int ide, int jds, int jde, int kde, int ims, int ime, int jms, int jme, int kms, int kme,          \
+    int its, int ite, int jts, int jte, int kts, int kte
+#define AMT_STAGE_DOMAIN(T)                                                                                     \
+    amt_domain d{(int)sizeof(T), 0, 0, 0, ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte}; \
+    d.stream = static_cast<hipStream_t>(hip_stream);
+#define AMT_STAGE_PREP_SIG(T)                                                                                   \
+    void *hip_stream, int members, T *t, T *t_1, T *t_old, const T *ww, T *ww_1, T *mu, T *mu_old, T *mu_save,  \
+    T *muts, T *mudf, const T *mut, const T *mub, int rk_step, AMT_STAGE_BOUNDS_SIG
+#define AMT_STAGE_FINISH_SIG(T)                                                                                 \
+    void *hip_stream, int members, T *t, const T *t_1, T *ww, const T *ww_1, T *mu, const T *mu_save,           \
+    const T *muts, const T *mut, T dts, int n_small_steps, const T *h_diabatic, AMT_STAGE_BOUNDS_SIG
+#define AMT_STAGE_PREP_BODY(T, name)                                                                            \
+    AMT_STAGE_DOMAIN(T)                                                                                         \
+    return stage_prep_run(name, d, members, StagePrepArrays{t, t_1, t_old, ww, ww_1, mu, mu_old, mu_save, muts, mudf, mut, mub}, rk_step, true);
+#define AMT_STAGE_FINISH_BODY(T, name)                                                                          \
+    AMT_STAGE_DOMAIN(T)                                                                                         \
+    return stage_finish_run(name, d, members, StageFinishArrays{t, t_1, ww, ww_1, mu, mu_save, muts, mut, h_diabatic}, (double)dts, n_small_steps, true);
+
+extern "C" int amt_stage_prep_device_f32(AMT_STAGE_PREP_SIG(float)) { AMT_STAGE_PREP_BODY(float, "amt_stage_prep_device_f32") }
+extern "C" int amt_stage_prep_device_f64(AMT_STAGE_PREP_SIG(double)) { AMT_STAGE_PREP_BODY(double, "amt_stage_prep_device_f64") }
+extern "C" int amt_stage_finish_device_f32(AMT_STAGE_FINISH_SIG(float)) { AMT_STAGE_FINISH_BODY(float, "amt_stage_finish_device_f32") }
+extern "C" int amt_stage_finish_device_f64(AMT_STAGE_FINISH_SIG(double)) { AMT_STAGE_FINISH_BODY(double, "amt_stage_finish_device_f64") }

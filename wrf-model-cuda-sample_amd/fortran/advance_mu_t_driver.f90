@@ -9,13 +9,15 @@
 ! domain handle (device arrays kept across calls -- the kernel-only time the
 ! reference reports) and checks that both paths agree bit for bit.
 !
-!   advance_mu_t_driver [NI NK NJ [nsweeps [outdir [flags [placements [members [nsmall]]]]]]]
+!   advance_mu_t_driver [NI NK NJ [nsweeps [outdir [flags [placements [members [nsmall [bracket]]]]]]]]
 !     flags: 0 none, 1 specified, 2 nested, 3 specified+periodic_x
 !     placements: > 1 samples that many allocations of the resident state and keeps the fastest (amt_domain_tune_placement)
 !     members: > 0 adds an ensemble of that many members of the same shape (amt_ensemble_fill_synthetic, seeds seed + m),
 !              stepped nsweeps times, and its mean / variance / envelope over the members (header section 13)
 !     nsmall: > 0 adds an acoustic loop of that many sub-steps on a resident handle with the flux averages ru_m, rv_m, ww_m
 !             accumulated on the device behind every sweep (header section 14), on a single patch and on an ensemble
+!     bracket: 1 with nsmall > 0 adds two Runge-Kutta stages on a resident handle whose acoustic loops of nsmall sub-steps run
+!              between small_step_prep and small_step_finish on the device (header section 15); 0 (the default): nothing more
 !   With outdir the 7 updated arrays are written there as raw native-endian
 !   streams <name>.bin for an external checker; with members the moments as ens_<field>_<mean|var|lo|hi>.bin:
 !   ww over the whole memory, mu over the compute window, t over the memory less one cell on every side (zero outside).
@@ -44,7 +46,7 @@ program advance_mu_t_driver
   real(c_float) :: ms
   integer(kind=8) :: c0, c1, cmid, hz
   real(kind=8) :: cells, secs
-  integer :: nbad, ndef, ntune, members, nsmall
+  integer :: nbad, ndef, ntune, members, nsmall, bracket
   integer(c_int) :: nslots, slot_ids(16)
   real(c_float) :: tune_ms(8)
 
@@ -73,6 +75,10 @@ program advance_mu_t_driver
   nsmall = 0
   if (command_argument_count() >= 9) then
      call get_command_argument(9, arg); read (arg, *) nsmall
+  end if
+  bracket = 0
+  if (command_argument_count() >= 10) then
+     call get_command_argument(10, arg); read (arg, *) bracket
   end if
   config_flags%specified  = (iflag == 1 .or. iflag == 3)
   config_flags%nested     = (iflag == 2)
@@ -278,8 +284,158 @@ program advance_mu_t_driver
 
   if (members > 0) call ensemble_moments()
   if (nsmall > 0) call flux_averages()
+  if (nsmall > 0 .and. bracket == 1) call stage_bracket()
 
 contains
+
+  ! Two Runge-Kutta stages (rk_step 1 without, rk_step 2 with a diabatic heating) whose acoustic loops of nsmall sub-steps run
+  ! between small_step_prep and small_step_finish on the device.  t_old, mu_old, mu_save, mub and h_diabatic are the caller's:
+  ! arrays of a second handle of the same shape serve (filled from the generator, they come down with amt_domain_download).
+  ! The same two stages are repeated with the pointer-level calls on a third handle and must give the same bits, and run on an
+  ! ensemble with member-stacked arrays.
+  subroutine stage_bracket()
+    type(c_ptr) :: d, d2, ex, e, eex
+    real(wp), allocatable, target :: a3(:,:,:), b3(:,:,:), a2(:,:), b2(:,:)
+    integer(c_int) :: wb, px, sp, ne, mm, rk, k
+    integer(c_int), parameter :: xf(4) = [AMT_F_T, AMT_F_MU, AMT_F_MUAVE, AMT_F_MUT]      ! of `ex`: t_old, mu_old, mu_save, mub
+    integer(c_int), parameter :: f3(4) = [AMT_F_T, AMT_F_WW, AMT_F_T_1, AMT_F_WW_1], f2(2) = [AMT_F_MU, AMT_F_MUTS]
+    character(len=4), parameter :: n3(4) = ['t   ', 'ww  ', 't_1 ', 'ww_1'], n2(2) = ['mu  ', 'muts']
+    character(len=7), parameter :: nx(4) = ['t_old  ', 'mu_old ', 'mu_save', 'mub    ']
+    wb = int(storage_size(rdx)/8, c_int)
+    px = merge(1_c_int, 0_c_int, config_flags%periodic_x)
+    sp = merge(1_c_int, 0_c_int, config_flags%specified)
+    ne = merge(1_c_int, 0_c_int, config_flags%nested)
+    mm = int(max(members, 1), c_int)
+    allocate (a3(ims:ime,kms:kme,jms:jme), b3(ims:ime,kms:kme,jms:jme), a2(ims:ime,jms:jme), b2(ims:ime,jms:jme))
+    call make_domain(d, seed)
+    call make_domain(d2, seed)
+    call make_domain(ex, seed + 1_c_int64_t)
+    ! handle level: off until set, a mix of given and missing arrays is refused, then the caller's four
+    if (c_associated(amt_domain_stage_ptr(d, 0_c_int))) error stop 8
+    if (amt_domain_stage_prep(d, 1_c_int) /= AMT_ERR_PRECONDITION) error stop 8
+    if (amt_domain_set_stage(d, 1_c_int, amt_domain_field_ptr(ex, xf(1)), c_null_ptr, c_null_ptr, c_null_ptr) /= AMT_ERR_INVALID_ARG) &
+       error stop 8
+    call amt_check(amt_domain_set_stage(d, 1_c_int, amt_domain_field_ptr(ex, xf(1)), amt_domain_field_ptr(ex, xf(2)),       &
+                   amt_domain_field_ptr(ex, xf(3)), amt_domain_field_ptr(ex, xf(4))), 'amt_domain_set_stage')
+    if (.not. c_associated(amt_domain_stage_ptr(d, 3_c_int), amt_domain_field_ptr(ex, xf(4)))) error stop 8
+    do rk = 1, 2
+       call amt_check(amt_domain_stage_prep(d, rk), 'amt_domain_stage_prep')
+       call amt_check(amt_domain_step(d, int(nsmall, c_int)), 'amt_domain_step')
+       call amt_check(amt_domain_stage_finish(d, int(nsmall, c_int), merge(amt_domain_field_ptr(ex, AMT_F_FT), c_null_ptr, rk == 2)), &
+                      'amt_domain_stage_finish')
+    end do
+    call amt_check(amt_domain_sync(d), 'amt_domain_sync')
+    ! pointer level on the third handle's arrays and stream: the same two stages
+    do rk = 1, 2
+       call stage_device(d2, ex, rk)
+    end do
+    call amt_check(amt_domain_sync(d2), 'amt_domain_sync')
+    print '(a,i0,a)', 'two Runge-Kutta stages of ', nsmall, ' sub-steps between small_step_prep and small_step_finish on the device'
+    do k = 1, 4
+       call amt_check(amt_domain_download(d, f3(k), c_loc(a3)), 'amt_domain_download')
+       call amt_check(amt_domain_download(d2, f3(k), c_loc(b3)), 'amt_domain_download')
+       if (any(transfer(a3, 1_c_int8_t, size(a3) * wb) /= transfer(b3, 1_c_int8_t, size(b3) * wb))) error stop 9
+       print '(a,a,a,es24.16)', 'checksum of ', n3(k), ' after the stages: ', sum(real(a3(its:ite-1, kts:kte-1, jts:jte-1), 8))
+       if (len_trim(outdir) > 0) call dump3('stage_'//trim(n3(k)), a3)
+    end do
+    do k = 1, 2
+       call amt_check(amt_domain_download(d, f2(k), c_loc(a2)), 'amt_domain_download')
+       call amt_check(amt_domain_download(d2, f2(k), c_loc(b2)), 'amt_domain_download')
+       if (any(transfer(a2, 1_c_int8_t, size(a2) * wb) /= transfer(b2, 1_c_int8_t, size(b2) * wb))) error stop 9
+       if (len_trim(outdir) > 0) call dump2('stage_'//trim(n2(k)), a2)
+    end do
+    if (len_trim(outdir) > 0) then
+       call amt_check(amt_domain_download(ex, xf(1), c_loc(a3)), 'amt_domain_download')
+       call dump3('stage_'//trim(nx(1)), a3)
+       do k = 2, 4
+          call amt_check(amt_domain_download(ex, xf(k), c_loc(a2)), 'amt_domain_download')
+          call dump2('stage_'//trim(nx(k)), a2)
+       end do
+    end if
+    call amt_check(amt_domain_set_stage(d, 0_c_int, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr), 'amt_domain_set_stage')
+    if (c_associated(amt_domain_stage_ptr(d, 3_c_int))) error stop 8
+    call amt_check(amt_domain_destroy(d), 'amt_domain_destroy')
+    call amt_check(amt_domain_destroy(d2), 'amt_domain_destroy')
+    call amt_check(amt_domain_destroy(ex), 'amt_domain_destroy')
+    ! an ensemble: every member's prep and finish in one launch each, the four arrays member-stacked in a second ensemble
+    call make_ensemble(e, mm, seed)
+    call make_ensemble(eex, mm, seed + 1_c_int64_t)
+    call amt_check(amt_ensemble_set_stage(e, 1_c_int, amt_ensemble_field_ptr(eex, xf(1)), amt_ensemble_field_ptr(eex, xf(2)),  &
+                   amt_ensemble_field_ptr(eex, xf(3)), amt_ensemble_field_ptr(eex, xf(4))), 'amt_ensemble_set_stage')
+    if (.not. c_associated(amt_ensemble_stage_ptr(e, 0_c_int), amt_ensemble_field_ptr(eex, xf(1)))) error stop 8
+    call amt_check(amt_ensemble_stage_prep(e, 1_c_int), 'amt_ensemble_stage_prep')
+    call amt_check(amt_ensemble_step(e, int(nsmall, c_int)), 'amt_ensemble_step')
+    call amt_check(amt_ensemble_stage_finish(e, int(nsmall, c_int), amt_ensemble_field_ptr(eex, AMT_F_FT)), 'amt_ensemble_stage_finish')
+    call amt_check(amt_ensemble_sync(e), 'amt_ensemble_sync')
+    print '(a,i0,a)', 'a Runge-Kutta stage of an ensemble of ', mm, ' members: one launch per pass'
+    call amt_check(amt_ensemble_destroy(e), 'amt_ensemble_destroy')
+    call amt_check(amt_ensemble_destroy(eex), 'amt_ensemble_destroy')
+  end subroutine
+
+  subroutine make_domain(h, fill_seed)
+    type(c_ptr), intent(out) :: h
+    integer(c_int64_t), intent(in) :: fill_seed
+    call amt_check(amt_domain_create(h, int(storage_size(rdx)/8, c_int), merge(1_c_int, 0_c_int, config_flags%periodic_x),     &
+                   merge(1_c_int, 0_c_int, config_flags%specified), merge(1_c_int, 0_c_int, config_flags%nested),            &
+                   ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte), 'amt_domain_create')
+    call amt_check(amt_domain_set_scalars(h, real(rdx, c_double), real(rdy, c_double), real(dts, c_double),                  &
+                                          real(epssm, c_double)), 'amt_domain_set_scalars')
+    call amt_check(amt_domain_fill_synthetic(h, fill_seed, int(ims, c_long), int(kms-1, c_long), int(jms, c_long),            &
+                   int(ni+2, c_long), int(nk+1, c_long), int(nj+2, c_long)), 'amt_domain_fill_synthetic')
+  end subroutine
+
+  subroutine make_ensemble(h, mm, fill_seed)
+    type(c_ptr), intent(out) :: h
+    integer(c_int), intent(in) :: mm
+    integer(c_int64_t), intent(in) :: fill_seed
+    call amt_check(amt_ensemble_create(h, mm, int(storage_size(rdx)/8, c_int), merge(1_c_int, 0_c_int, config_flags%periodic_x), &
+                   merge(1_c_int, 0_c_int, config_flags%specified), merge(1_c_int, 0_c_int, config_flags%nested),            &
+                   ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte), 'amt_ensemble_create')
+    call amt_check(amt_ensemble_set_scalars(h, real(rdx, c_double), real(rdy, c_double), real(dts, c_double),                &
+                                            real(epssm, c_double)), 'amt_ensemble_set_scalars')
+    call amt_check(amt_ensemble_fill_synthetic(h, fill_seed, int(ims, c_long), int(kms-1, c_long), int(jms, c_long),          &
+                   int(ni+2, c_long), int(nk+1, c_long), int(nj+2, c_long)), 'amt_ensemble_fill_synthetic')
+  end subroutine
+
+  ! one stage on handle h's arrays with the pointer-level calls, on h's stream: prep, nsmall sweeps of the handle, finish
+  subroutine stage_device(h, ex, rk)
+    type(c_ptr), intent(in) :: h, ex
+    integer(c_int), intent(in) :: rk
+    type(c_ptr) :: p(0:25), stream, heat
+    integer(c_int) :: f
+    do f = 0, 25
+       p(f) = amt_domain_field_ptr(h, f)
+    end do
+    stream = amt_domain_stream(h)
+    heat = merge(amt_domain_field_ptr(ex, AMT_F_FT), c_null_ptr, rk == 2)
+    if (storage_size(rdx) == 64) then
+       rc = amt_stage_prep_device_f64(stream, 1_c_int, p(AMT_F_T), p(AMT_F_T_1), amt_domain_field_ptr(ex, AMT_F_T), p(AMT_F_WW), &
+                                      p(AMT_F_WW_1), p(AMT_F_MU), amt_domain_field_ptr(ex, AMT_F_MU),                       &
+                                      amt_domain_field_ptr(ex, AMT_F_MUAVE), p(AMT_F_MUTS), p(AMT_F_MUDF), p(AMT_F_MUT),      &
+                                      amt_domain_field_ptr(ex, AMT_F_MUT), rk,                                              &
+                                      ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte)
+    else
+       rc = amt_stage_prep_device_f32(stream, 1_c_int, p(AMT_F_T), p(AMT_F_T_1), amt_domain_field_ptr(ex, AMT_F_T), p(AMT_F_WW), &
+                                      p(AMT_F_WW_1), p(AMT_F_MU), amt_domain_field_ptr(ex, AMT_F_MU),                       &
+                                      amt_domain_field_ptr(ex, AMT_F_MUAVE), p(AMT_F_MUTS), p(AMT_F_MUDF), p(AMT_F_MUT),      &
+                                      amt_domain_field_ptr(ex, AMT_F_MUT), rk,                                              &
+                                      ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte)
+    end if
+    call amt_check(rc, 'amt_stage_prep_device')
+    call amt_check(amt_domain_step(h, int(nsmall, c_int)), 'amt_domain_step')
+    if (storage_size(rdx) == 64) then
+       rc = amt_stage_finish_device_f64(stream, 1_c_int, p(AMT_F_T), p(AMT_F_T_1), p(AMT_F_WW), p(AMT_F_WW_1), p(AMT_F_MU),    &
+                                        amt_domain_field_ptr(ex, AMT_F_MUAVE), p(AMT_F_MUTS), p(AMT_F_MUT),                  &
+                                        real(dts, c_double), int(nsmall, c_int), heat,                                      &
+                                        ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte)
+    else
+       rc = amt_stage_finish_device_f32(stream, 1_c_int, p(AMT_F_T), p(AMT_F_T_1), p(AMT_F_WW), p(AMT_F_WW_1), p(AMT_F_MU),    &
+                                        amt_domain_field_ptr(ex, AMT_F_MUAVE), p(AMT_F_MUTS), p(AMT_F_MUT),                  &
+                                        real(dts, c_float), int(nsmall, c_int), heat,                                       &
+                                        ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte)
+    end if
+    call amt_check(rc, 'amt_stage_finish_device')
+  end subroutine
 
   ! One acoustic loop of nsmall sub-steps with the flux averages kept on the device: the handle accumulates behind every sweep
   ! into arrays the library allocates; the same loop is then repeated with the pointer-level call into caller-owned arrays (the

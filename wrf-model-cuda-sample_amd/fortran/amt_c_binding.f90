@@ -7,6 +7,8 @@ MODULE amt_c_binding
    implicit none
 
    integer(c_int), parameter :: AMT_OK = 0
+   integer(c_int), parameter :: AMT_ERR_PRECONDITION = 2      ! bounds, or a call the handle's settings do not admit
+   integer(c_int), parameter :: AMT_ERR_INVALID_ARG = 3       ! a null pointer, a bad id or count
    integer(c_int), parameter :: AMT_ERR_NONFINITE = 7         ! the non-finite guard of header section 10 has a finding
    ! enum amt_variant (amt_*_set_variant, the `variant` argument of amt_advance_mu_t_device_* and its ensemble twin);
    ! AMT_LAUNCH_BESIDE_OTHERS is OR-ed into that argument
@@ -1095,6 +1097,118 @@ MODULE amt_c_binding
          type(c_ptr), value :: handle
          integer(c_int), value :: which
          type(c_ptr) :: ptr
+      end function
+      ! (15) the bracket of a Runge-Kutta stage: small_step_prep in front of a stage's acoustic loop, small_step_finish behind it.
+      ! Pointer level (members = 1 for a single patch): every array is a DEVICE pointer; asynchronous on hip_stream.  t_old,
+      ! mu_old, mu_save, mub and h_diabatic are not AMT_F_* fields; mudf may be c_null_ptr at rk_step > 1
+      function amt_stage_prep_device_f32(hip_stream, members, t, t_1, t_old, ww, ww_1, mu, mu_old, mu_save, muts, mudf,     &
+                                         mut, mub, rk_step, ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,       &
+                                         its, ite, jts, jte, kts, kte) bind(C, name="amt_stage_prep_device_f32") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: hip_stream
+         integer(c_int), value :: members
+         type(c_ptr), value :: t, t_1, t_old, ww, ww_1, mu, mu_old, mu_save, muts, mudf, mut, mub        ! device pointers
+         integer(c_int), value :: rk_step
+         integer(c_int), value :: ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme
+         integer(c_int), value :: its, ite, jts, jte, kts, kte
+         integer(c_int) :: rc
+      end function
+      function amt_stage_prep_device_f64(hip_stream, members, t, t_1, t_old, ww, ww_1, mu, mu_old, mu_save, muts, mudf,     &
+                                         mut, mub, rk_step, ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,       &
+                                         its, ite, jts, jte, kts, kte) bind(C, name="amt_stage_prep_device_f64") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: hip_stream
+         integer(c_int), value :: members
+         type(c_ptr), value :: t, t_1, t_old, ww, ww_1, mu, mu_old, mu_save, muts, mudf, mut, mub        ! device pointers
+         integer(c_int), value :: rk_step
+         integer(c_int), value :: ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme
+         integer(c_int), value :: its, ite, jts, jte, kts, kte
+         integer(c_int) :: rc
+      end function
+      function amt_stage_finish_device_f32(hip_stream, members, t, t_1, ww, ww_1, mu, mu_save, muts, mut, dts,             &
+                                           n_small_steps, h_diabatic, ids, ide, jds, jde, kde, ims, ime, jms, jme,       &
+                                           kms, kme, its, ite, jts, jte, kts, kte)                                       &
+                                           bind(C, name="amt_stage_finish_device_f32") result(rc)
+         import :: c_ptr, c_int, c_float
+         type(c_ptr), value :: hip_stream
+         integer(c_int), value :: members
+         type(c_ptr), value :: t, t_1, ww, ww_1, mu, mu_save, muts, mut                                  ! device pointers
+         real(c_float), value :: dts
+         integer(c_int), value :: n_small_steps
+         type(c_ptr), value :: h_diabatic                                                                ! device pointer or c_null_ptr
+         integer(c_int), value :: ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme
+         integer(c_int), value :: its, ite, jts, jte, kts, kte
+         integer(c_int) :: rc
+      end function
+      function amt_stage_finish_device_f64(hip_stream, members, t, t_1, ww, ww_1, mu, mu_save, muts, mut, dts,             &
+                                           n_small_steps, h_diabatic, ids, ide, jds, jde, kde, ims, ime, jms, jme,       &
+                                           kms, kme, its, ite, jts, jte, kts, kte)                                       &
+                                           bind(C, name="amt_stage_finish_device_f64") result(rc)
+         import :: c_ptr, c_int, c_double
+         type(c_ptr), value :: hip_stream
+         integer(c_int), value :: members
+         type(c_ptr), value :: t, t_1, ww, ww_1, mu, mu_save, muts, mut                                  ! device pointers
+         real(c_double), value :: dts
+         integer(c_int), value :: n_small_steps
+         type(c_ptr), value :: h_diabatic                                                                ! device pointer or c_null_ptr
+         integer(c_int), value :: ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme
+         integer(c_int), value :: its, ite, jts, jte, kts, kte
+         integer(c_int) :: rc
+      end function
+      ! set: on = 0 off (the default); on = 1 with four c_null_ptr: the library allocates t_old, mu_old, mu_save, mub (the host
+      ! fills mub through amt_domain_stage_ptr), with four device pointers: the caller's.  prep and finish are then issued on the
+      ! handle around the stage's sweeps (amt_domain_step, amt_slab_step, amt_grid_step ...); finish uses the handle's dts
+      function amt_domain_set_stage(handle, on, t_old, mu_old, mu_save, mub) bind(C, name="amt_domain_set_stage") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: on
+         type(c_ptr), value :: t_old, mu_old, mu_save, mub
+         integer(c_int) :: rc
+      end function
+      function amt_domain_stage_ptr(handle, which) bind(C, name="amt_domain_stage_ptr") result(ptr)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: which                                              ! 0 t_old, 1 mu_old, 2 mu_save, 3 mub
+         type(c_ptr) :: ptr
+      end function
+      function amt_domain_stage_prep(handle, rk_step) bind(C, name="amt_domain_stage_prep") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: rk_step
+         integer(c_int) :: rc
+      end function
+      function amt_domain_stage_finish(handle, n_small_steps, h_diabatic) bind(C, name="amt_domain_stage_finish") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: n_small_steps
+         type(c_ptr), value :: h_diabatic                                            ! device pointer or c_null_ptr
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_set_stage(handle, on, t_old, mu_old, mu_save, mub) bind(C, name="amt_ensemble_set_stage") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: on
+         type(c_ptr), value :: t_old, mu_old, mu_save, mub
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_stage_ptr(handle, which) bind(C, name="amt_ensemble_stage_ptr") result(ptr)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: which                                              ! 0 t_old, 1 mu_old, 2 mu_save, 3 mub
+         type(c_ptr) :: ptr
+      end function
+      function amt_ensemble_stage_prep(handle, rk_step) bind(C, name="amt_ensemble_stage_prep") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: rk_step
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_stage_finish(handle, n_small_steps, h_diabatic) bind(C, name="amt_ensemble_stage_finish") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: n_small_steps
+         type(c_ptr), value :: h_diabatic                                            ! device pointer or c_null_ptr
+         integer(c_int) :: rc
       end function
    end interface
 

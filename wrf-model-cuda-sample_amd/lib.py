@@ -212,6 +212,18 @@ SYMBOLS = {
     "amt_ensemble_sumflux_accumulate": (_I, [_P]),
     "amt_ensemble_sumflux_state": (_I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "amt_ensemble_sumflux_ptr": (_P, [_P, _I]),
+    "amt_stage_prep_device_f32": (_I, [_P, _I] + [_P] * 12 + [_I] * (1 + 17)),
+    "amt_stage_prep_device_f64": (_I, [_P, _I] + [_P] * 12 + [_I] * (1 + 17)),
+    "amt_stage_finish_device_f32": (_I, [_P, _I] + [_P] * 8 + [ctypes.c_float, _I, _P] + [_I] * 17),
+    "amt_stage_finish_device_f64": (_I, [_P, _I] + [_P] * 8 + [ctypes.c_double, _I, _P] + [_I] * 17),
+    "amt_domain_set_stage": (_I, [_P, _I, _P, _P, _P, _P]),
+    "amt_domain_stage_ptr": (_P, [_P, _I]),
+    "amt_domain_stage_prep": (_I, [_P, _I]),
+    "amt_domain_stage_finish": (_I, [_P, _I, _P]),
+    "amt_ensemble_set_stage": (_I, [_P, _I, _P, _P, _P, _P]),
+    "amt_ensemble_stage_ptr": (_P, [_P, _I]),
+    "amt_ensemble_stage_prep": (_I, [_P, _I]),
+    "amt_ensemble_stage_finish": (_I, [_P, _I, _P]),
     "amt_halo_plan": (_I, [_I] * (4 + 17 + 5) + [ctypes.POINTER(HaloMessage), _I, ctypes.POINTER(_I)]),
     "amt_grid_halo_messages": (_I, [_P, ctypes.POINTER(HaloMessage), _I, ctypes.POINTER(_I)]),
     "amt_slab_halo_messages": (_I, [_P, ctypes.POINTER(HaloMessage), _I, ctypes.POINTER(_I)]),
@@ -277,7 +289,7 @@ class DeviceView:
 
 
 class ResidentHandle:
-    """What a resident handle does whichever kind it is (header sections 4, 8, 9, 10, 12, 14): stepping, the per-sweep settings,
+    """What a resident handle does whichever kind it is (header sections 4, 8, 9, 10, 12, 14, 15): stepping, the per-sweep settings,
     the diagnostics and the release.  The owning class names its C functions' prefix (``amt_domain`` / ``amt_ensemble``) in
     ``_PREFIX`` and its member count in ``_members()``, and holds the library in ``L`` and the handle in ``handle``.  The stepping
     methods pass their status through ``_check`` so that an ERR_NONFINITE error carries the guard's report."""
@@ -402,6 +414,32 @@ class ResidentHandle:
     def sumflux_ptr(self, which: int) -> int:
         """Device address of ru_m (0), rv_m (1) or ww_m (2); 0 while the setting is off."""
         return int(self._fn("sumflux_ptr")(self.handle, int(which)) or 0)
+
+    # the bracket of a Runge-Kutta stage: small_step_prep and small_step_finish (header section 15)
+    def set_stage(self, on: bool = True, t_old=None, mu_old=None, mu_save=None, mub=None) -> None:
+        """``set_stage``: False = off.  Without arrays the library allocates ``t_old`` (one 3-D field's extents) and ``mu_old``,
+        ``mu_save``, ``mub`` (one 2-D field's, all times the members); otherwise all four are device tensors (or addresses) which
+        the caller keeps alive.  ``mub`` is a pure input: fill it once (``stage_ptr(3)``)."""
+        check(self._fn("set_stage")(self.handle, int(bool(on)), *[_address(a) for a in (t_old, mu_old, mu_save, mub)]))
+
+    def stage_ptr(self, which: int) -> int:
+        """Device address of t_old (0), mu_old (1), mu_save (2) or mub (3); 0 while the setting is off."""
+        return int(self._fn("stage_ptr")(self.handle, int(which)) or 0)
+
+    def stage_prep(self, rk_step: int) -> None:
+        """``stage_prep``: small_step_prep of Runge-Kutta step ``rk_step`` >= 1 in front of the stage's acoustic loop,
+        asynchronous on the handle's stream (every member of an ensemble in one launch)."""
+        check(self._fn("stage_prep")(self.handle, int(rk_step)))
+
+    def stage_finish(self, n_small_steps: int, h_diabatic=None) -> None:
+        """``stage_finish``: small_step_finish behind a loop of ``n_small_steps`` sweeps, with the handle's dts;
+        ``h_diabatic``: a device tensor (or address) of one 3-D field's extents, or None."""
+        check(self._fn("stage_finish")(self.handle, int(n_small_steps), _address(h_diabatic)))
+
+
+def _address(a):
+    """A device tensor, an address or None as a ``c_void_p``."""
+    return ctypes.c_void_p(None if a is None else a.data_ptr() if hasattr(a, "data_ptr") else int(a))
 
 
 HandleDiag = ResidentHandle          # the name this class had while it held the diagnostics only

@@ -490,6 +490,34 @@ class _NativeStepper:
             out.append(torch.as_tensor(view, device=t0.device))
         return tuple(out)
 
+    # The bracket of a Runge-Kutta stage (header section 15) on this rank's own tile: issued on the domain handle between the
+    # stepper's step calls, ordered by the domain's stream; nothing is exchanged for it (the halo exchange carries t_1).
+    def set_stage(self, on: bool = True):
+        """The library allocates t_old, mu_old, mu_save, mub (``stage_arrays``); False frees them."""
+        with self._dev():
+            self._lib.check(self.L.amt_domain_set_stage(self._dom, int(bool(on)), None, None, None, None))
+
+    def stage_arrays(self):
+        """t_old, mu_old, mu_save, mub as torch tensors that view the library's device arrays (valid while the stepper lives)."""
+        import torch
+        b, t0 = self.patch.bounds, self.patch.arrays["t_1"]
+        out = []
+        for which in range(4):
+            ptr = self.L.amt_domain_stage_ptr(self._dom, which)
+            if not ptr:
+                raise self._lib.AmtError(self._lib.ERR_PRECONDITION, "the stage bracket is off")
+            view = self._lib.DeviceView(self, ptr, b.shape("t" if which == 0 else "mu"), "<f8" if t0.element_size() == 8 else "<f4")
+            out.append(torch.as_tensor(view, device=t0.device))
+        return tuple(out)
+
+    def stage_prep(self, rk_step: int):
+        with self._dev():
+            self._lib.check(self.L.amt_domain_stage_prep(self._dom, int(rk_step)))
+
+    def stage_finish(self, n_small_steps: int, h_diabatic=None):
+        with self._dev():
+            self._lib.check(self.L.amt_domain_stage_finish(self._dom, int(n_small_steps), self._lib._address(h_diabatic)))
+
     def close(self):
         if self._h:
             with self._dev():
