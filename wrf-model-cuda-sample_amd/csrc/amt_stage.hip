@@ -14,6 +14,7 @@
 // launches in stream order, the 3-D pass first (it never reads the stored muts), and finish, which has no such dependency, is
 // ONE.  Separate streaming passes around the acoustic loop: the march kernel is not touched.
 #include "amt_internal.h"
+#include "amt_chunk_index.h"
 
 namespace {
 // A job works on a box of nk * nj runs of `ni` contiguous elements, run r = (k, j) = (r % nk, r / nk) of member m starting at
@@ -41,20 +42,10 @@ template <int kPer>
 __device__ __forceinline__ void amt_stage_chunk(long e, long chunks, long nk, long ni, bool narrow, long idim, long jstride3,
                                                 long &at3, long &at2, int &cnt)
 {
-    long r, j;
-    if (narrow) {                                                  // wave-uniform: 32-bit divisions where they suffice
-        r = (long)((unsigned)e / (unsigned)chunks);
-        j = (long)((unsigned)r / (unsigned)nk);
-    } else {
-        r = e / chunks;
-        j = r / nk;
-    }
-    const long k = r - j * nk;
-    const long i0 = (e - r * chunks) * kPer;
-    at3 = j * jstride3 + k * idim + i0;
-    at2 = j * idim + i0;
-    const long left = ni - i0;
-    cnt = left < kPer ? (int)left : kPer;
+    const AmtChunk c = amt_chunk_index<kPer>(e, chunks, nk, ni, narrow);   // narrow is wave-uniform
+    at3 = c.j * jstride3 + c.k * idim + c.i0;
+    at2 = c.j * idim + c.i0;
+    cnt = c.cnt;
 }
 
 // The common 16-byte phase of a job's 3-D streams behind the member offset (wave-uniform), or -1 where they differ.  A chunk at

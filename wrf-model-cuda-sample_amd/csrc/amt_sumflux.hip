@@ -8,6 +8,7 @@
 // one short of the domain's end); at iteration 1 the tile's cells outside it become +0.0.  ONE launch does the three
 // accumulators, times the members of an ensemble.  A separate streaming pass behind the sweep: the march kernel is not touched.
 #include "amt_internal.h"
+#include "amt_chunk_index.h"
 
 namespace {
 enum { AMT_SUMFLUX_JOBS = 3 };              // ru_m, rv_m, ww_m
@@ -66,19 +67,10 @@ __global__ __launch_bounds__(256) void amt_sumflux_kernel(AmtSumfluxJobs<T> jobs
     const long total = nk * (long)jobs.nj * chunks;
     const bool narrow = total <= 0x7fffffffL;                      // wave-uniform: 32-bit divisions where they suffice
     for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-        long r, j;
-        if (narrow) {
-            r = (long)((unsigned)e / (unsigned)chunks);
-            j = (long)((unsigned)r / (unsigned)nk);
-        } else {
-            r = e / chunks;
-            j = r / nk;
-        }
-        const long k = r - j * nk;
-        const long i0 = (e - r * chunks) * kPer;                   // first element of this chunk inside its run
+        const AmtChunk c = amt_chunk_index<kPer>(e, chunks, nk, ni, narrow);
+        const long j = c.j, k = c.k, i0 = c.i0;                    // i0: first element of this chunk inside its run
         const long at3 = j * jobs.jstride3 + k * jobs.idim + i0, at2 = j * jobs.idim + i0;
-        const long left = ni - i0;
-        const int cnt = left < kPer ? (int)left : kPer;
+        const int cnt = c.cnt;
         T *a = acc + at3;
         if (k >= klen || j >= jlen) {                              // a run of the tile outside the accumulator's range
             if (first) {
