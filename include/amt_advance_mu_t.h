@@ -1066,6 +1066,81 @@ void *amt_ensemble_stage_ptr(amt_ensemble *e, int which);
 int amt_ensemble_stage_prep(amt_ensemble *e, int rk_step);
 int amt_ensemble_stage_finish(amt_ensemble *e, int n_small_steps, const void *h_diabatic);
 
+/* ------------------------------------------------------------------------
+ * (16) The pressure diagnosis that closes an acoustic sub-step: calc_p_rho, on the device.  In solve_em calc_p_rho follows
+ *      small_step_prep (with step = 0) and every advance_mu_t of the acoustic loop (step != 0): from t, mu and muts it diagnoses
+ *      the inverse density al and the pressure p that the next advance_uv reads, and in its hydrostatic branch integrates the
+ *      geopotential ph up the column.  With it prep (15) -> calc_p_rho(0) -> n x (sweep -> zone update (12) -> accumulation (14)
+ *      -> calc_p_rho) -> finish runs without a host round trip.  The reference has no source for the routine: the definition
+ *      below is this library's contract, modelled on WRF's routine (without the hybrid coordinate's c1h, c2h) and restricted to
+ *      the arrays the library owns.  WRF's names: t = t_2, t_old = t_1 (the array of (15)), mu = mu_2.  3-D arrays that are
+ *      not AMT_F_* fields: al, p, pm1 (outputs), ph (on w levels kts..kte; an input in mode 1, an output above kts in mode 2),
+ *      alt, c2a (pure inputs).  1-D arrays over kms..kme: rdnw (a handle uses its own metric), znu, dnw.  `members` >= 1
+ *      patches are member-stacked as in (8); the 1-D arrays are shared by the members.
+ *      Indices are Fortran-inclusive and global, on a tile its..ite, jts..jte with kts == 1 and kte == kde;
+ *      ihi = min(ite, ide-1), jhi = min(jte, jde-1); columns i = its..ihi, j = jts..jhi, cells k = kts..kte-1; T is the arrays'
+ *      type.  Every operation is rounded once in T, there is no fused multiply-add, divides are IEEE divides (no reciprocal
+ *      approximation), expressions associate exactly as written; for fp32 t0 and smdiv are rounded to float first.
+ *      Every cell computes   q = (alt * (t - (mu * t_old))) / (muts * (t0 + t_old))
+ *      MODE 1, non-hydrostatic:  al = (T(-1) / muts) * ((alt * mu) + (rdnw(k) * (ph(k+1) - ph(k))))
+ *                                p  = c2a * (q - al)                                            ph is not written
+ *      MODE 2, hydrostatic, k ascending:
+ *                                p  = mu * znu(k)
+ *                                al = q - (p / c2a)
+ *                                ph(k+1) = ph(k) - (dnw(k) * ((muts * al) + (mu * alt)))
+ *                                ph(k) is the value just written for k > kts; ph(kts) is read and never written
+ *      DIVERGENCE DAMPING, both modes, on the p just computed (x):
+ *        step == 0:  p = x;  pm1 = x                       (the old pm1 is not read and may hold NaN)
+ *        step != 0:  p = x + (smdiv * (x - pm1));  pm1 = x
+ *        in mode 2 al and ph use the undamped x.
+ *      Always bit-unchanged, NaN payloads included: everything outside the columns (column ide and row jde of a tile that
+ *      reaches them too), level kte of al, p, pm1, every memory level outside kts..kte, every input.  No input cell outside
+ *      the ranges is read (halos may hold NaN), nothing outside the arrays is touched.  No atomics, no workspace.  Inputs may
+ *      alias one another; an output overlaps no other array of the call.  One launch.
+ *      Reported before any device call, with or without a device, the arrays untouched:
+ *      AMT_ERR_INVALID_ARG: a NULL array; members < 1; a mode other than 1 or 2; step < 0; an output that overlaps another
+ *      array.  AMT_ERR_PRECONDITION: the tile outside memory; kts != 1; kte != kde; kme < kte; more than 65535 members.
+ *      NOT provided: the one-shot host-array calls of (1); advance_uv and advance_w; WRF's hybrid-coordinate (c1h, c2h) form;
+ *      filling or exchanging the halo cells of p, al, ph that advance_uv will read at i-1, j-1.
+ * ------------------------------------------------------------------------ */
+/* pointer level; asynchronous on hip_stream (NULL = the default stream) */
+int amt_p_rho_device_f32(
+    void *hip_stream, int members, int mode, int step, float *al, float *p, float *ph, float *pm1,
+    const float *alt, const float *c2a, const float *t, const float *t_old, const float *mu, const float *muts,
+    const float *rdnw, const float *znu, const float *dnw, float t0, float smdiv,
+    int ids, int ide, int jds, int jde, int kde,
+    int ims, int ime, int jms, int jme, int kms, int kme,
+    int its, int ite, int jts, int jte, int kts, int kte);
+int amt_p_rho_device_f64(
+    void *hip_stream, int members, int mode, int step, double *al, double *p, double *ph, double *pm1,
+    const double *alt, const double *c2a, const double *t, const double *t_old, const double *mu, const double *muts,
+    const double *rdnw, const double *znu, const double *dnw, double t0, double smdiv,
+    int ids, int ide, int jds, int jde, int kde,
+    int ims, int ime, int jms, int jme, int kms, int kme,
+    int its, int ite, int jts, int jte, int kts, int kte);
+/* mode = 0: off (the default) and what the library allocated is freed; the handle's destroy frees it too.  mode = 1 or 2 with
+ * al, p, ph, pm1, alt, c2a, znu, dnw all NULL: the library allocates the eight arrays (the six 3-D ones of a 3-D field's extents
+ * times the members of an ensemble, znu and dnw of kme-kms+1 elements; the host then fills alt, c2a, ph, znu, dnw through
+ * amt_domain_p_rho_ptr); all eight given: the caller's device arrays are used and never freed; a mix is AMT_ERR_INVALID_ARG.
+ * (The library's own eight, as amt_domain_p_rho_ptr returns them, may be handed back: mode, per_sweep, t0 and smdiv are set
+ * anew.)  The setting needs the stage setting of (15) on, whose t_old it reads: AMT_ERR_PRECONDITION otherwise, also from
+ * amt_domain_p_rho after amt_domain_set_stage(d, 0, ...).  A refusal changes nothing.
+ * per_sweep != 0: every sweep of amt_domain_step / amt_domain_step_timed is followed by one diagnosis with step != 0, behind
+ * the boundary-zone update (12) and the flux accumulation (14) and in front of the guard's checks (10), where WRF has it.  Under
+ * amt_slab_* and amt_grid_* it is enqueued exactly where the accumulation of the rank's own tile is, for every schedule and
+ * for *_step_end; nothing is exchanged.  amt_domain_tune_placement's timed sweeps are not followed by it. */
+int amt_domain_set_p_rho(amt_domain *d, int mode, int per_sweep, double t0, double smdiv,
+                         void *al, void *p, void *ph, void *pm1, void *alt, void *c2a, void *znu, void *dnw);
+void *amt_domain_p_rho_ptr(amt_domain *d, int which);   /* 0 al, 1 p, 2 ph, 3 pm1, 4 alt, 5 c2a, 6 znu, 7 dnw; NULL while off */
+/* one diagnosis now, asynchronous on the handle's stream (the caller's for a wrapped handle): the step = 0 call behind
+ * amt_domain_stage_prep, or any other; AMT_ERR_PRECONDITION while off */
+int amt_domain_p_rho(amt_domain *d, int step);
+/* the same for an ensemble: all members in one launch, member-stacked 3-D arrays, shared znu and dnw */
+int amt_ensemble_set_p_rho(amt_ensemble *e, int mode, int per_sweep, double t0, double smdiv,
+                           void *al, void *p, void *ph, void *pm1, void *alt, void *c2a, void *znu, void *dnw);
+void *amt_ensemble_p_rho_ptr(amt_ensemble *e, int which);
+int amt_ensemble_p_rho(amt_ensemble *e, int step);
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,7 +110,7 @@ def cyclic_fill(u, u_1, v, v_1, t_1, muu, muv, msfuy, msfvx_inv, config_flags,
     if dt not in (torch.float32, torch.float64):
         raise TypeError(f"unsupported dtype {dt}")
     for a, n in zip(arrays, want):
-        if not (_is_torch(a) and a.is_cuda and a.dtype == dt and a.is_contiguous() and a.numel() == n * int(members)):
+        if not (_is_torch(a) and a.is_cuda and a.dtype == dt and a.is_contiguous() and a.numel() == (-n if n < 0 else n * int(members))):
             raise TypeError("cyclic_fill needs contiguous CUDA tensors of one dtype and of the memory extents")
     if stream is None:
         stream = torch.cuda.current_stream(t_1.device)
@@ -139,7 +139,7 @@ def spec_bdy_update(t, ft, mu, muts, mu_tend, dts, config_flags,
     if dt not in (torch.float32, torch.float64):
         raise TypeError(f"unsupported dtype {dt}")
     for a, n in zip(arrays, want):
-        if not (_is_torch(a) and a.is_cuda and a.dtype == dt and a.is_contiguous() and a.numel() == n * int(members)):
+        if not (_is_torch(a) and a.is_cuda and a.dtype == dt and a.is_contiguous() and a.numel() == (-n if n < 0 else n * int(members))):
             raise TypeError("spec_bdy_update needs contiguous CUDA tensors of one dtype and of the memory extents")
     if stream is None:
         stream = torch.cuda.current_stream(t.device)
@@ -169,7 +169,7 @@ def sumflux(ru_m, rv_m, ww_m, u, v, ww, u_1, v_1, ww_1, muu, muv, msfuy, msfvx_i
     if dt not in (torch.float32, torch.float64):
         raise TypeError(f"unsupported dtype {dt}")
     for a, n in zip(arrays, want):
-        if not (_is_torch(a) and a.is_cuda and a.dtype == dt and a.is_contiguous() and a.numel() == n * int(members)):
+        if not (_is_torch(a) and a.is_cuda and a.dtype == dt and a.is_contiguous() and a.numel() == (-n if n < 0 else n * int(members))):
             raise TypeError("sumflux needs contiguous CUDA tensors of one dtype and of the memory extents")
     if stream is None:
         stream = torch.cuda.current_stream(ru_m.device)
@@ -184,7 +184,8 @@ def sumflux(ru_m, rv_m, ww_m, u, v, ww, u_1, v_1, ww_1, muu, muv, msfuy, msfvx_i
 
 def _stage_call(what, fn32, fn64, arrays, optional, sizes, members, stream, dtype, middle, bounds):
     """The checks and the call ``stage_prep`` and ``stage_finish`` share: ``arrays`` are torch device tensors or device addresses
-    (then ``dtype`` names the element type), an entry of ``optional`` may be None."""
+    (then ``dtype`` names the element type), an entry of ``optional`` may be None.  ``sizes`` are elements per member; a negative
+    one is an array the members share."""
     import torch
     L = _lib.load_library()
     tensors = [a for a in arrays if _is_torch(a)]
@@ -195,7 +196,7 @@ def _stage_call(what, fn32, fn64, arrays, optional, sizes, members, stream, dtyp
         if a is None and k in optional:
             continue
         if _is_torch(a):
-            if not (a.is_cuda and a.dtype == dt and a.is_contiguous() and a.numel() == n * int(members)):
+            if not (a.is_cuda and a.dtype == dt and a.is_contiguous() and a.numel() == (-n if n < 0 else n * int(members))):
                 raise TypeError(f"{what} needs contiguous CUDA tensors of one dtype and of the memory extents")
         elif not isinstance(a, int):
             raise TypeError(f"{what} needs CUDA tensors or device addresses")
@@ -237,6 +238,23 @@ def stage_finish(t, t_1, ww, ww_1, mu, mu_save, muts, mut, dts, n_small_steps, h
     _stage_call("stage_finish", L.amt_stage_finish_device_f32, L.amt_stage_finish_device_f64,
                 (t, t_1, ww, ww_1, mu, mu_save, muts, mut, h_diabatic), {8}, [n3] * 4 + [n2] * 4 + [n3], members, stream, dtype,
                 lambda p: p[:8] + [float(dts), int(n_small_steps), p[8]],
+                (ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte))
+
+
+def p_rho(mode, step, al, p, ph, pm1, alt, c2a, t, t_old, mu, muts, rdnw, znu, dnw, t0, smdiv,
+          ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,
+          its, ite, jts, jte, kts, kte, *, members=1, stream=None, dtype=None):
+    """calc_p_rho behind acoustic sub-step ``step`` (``amt_p_rho_device_f32/_f64``, header section 16) on a patch's (``members``
+    > 1: a member-stacked ensemble's) torch device tensors or device addresses (then with ``dtype``): ``al`` and ``p`` are
+    diagnosed from ``t``, ``t_old``, ``mu``, ``muts``; ``mode`` 1 reads ``ph``, ``mode`` 2 integrates it up the column; ``p`` is
+    damped against ``pm1`` at ``step`` != 0.  ``rdnw``, ``znu``, ``dnw`` are level arrays the members share.  Asynchronous on
+    ``stream`` (default: torch's current)."""
+    L = _lib.load_library()
+    n3, n2, n1 = (jme - jms + 1) * (kme - kms + 1) * (ime - ims + 1), (jme - jms + 1) * (ime - ims + 1), kme - kms + 1
+    arrays = (al, p, ph, pm1, alt, c2a, t, t_old, mu, muts, rdnw, znu, dnw)
+    _stage_call("p_rho", L.amt_p_rho_device_f32, L.amt_p_rho_device_f64, arrays, set(),
+                [n3] * 8 + [n2] * 2 + [-n1] * 3, members, stream, dtype,
+                lambda q: [int(mode), int(step)] + q + [float(t0), float(smdiv)],
                 (ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte))
 
 

@@ -20,6 +20,7 @@ void amt_handle_close(amt_domain *d)
     DeviceScope scope(d->device);
     amt_diag_release(d);
     amt_sumflux_release(d);
+    amt_p_rho_release(d);
     amt_stage_release(d);
     if (d->owns_fields)
         for (void *&q : d->field)
@@ -327,7 +328,9 @@ int amt_handle_behind_sweep(const char *who, amt_domain *d, int members)
     // specified / nested boundaries: the boundary zone is advanced behind the sweep, where WRF has its spec_bdyupdate calls
     const int rc = d->spec_bdy ? amt_bdy_update_domain(who, d, members) : AMT_OK;
     // the acoustic loop's flux averages: one accumulation behind the boundary-zone update, where WRF has its sumflux call
-    return rc == AMT_OK && d->sumflux_n ? amt_sumflux_accumulate_domain(who, d, members) : rc;
+    const int rc2 = rc == AMT_OK && d->sumflux_n ? amt_sumflux_accumulate_domain(who, d, members) : rc;
+    // the pressure diagnosis closes the sub-step, where WRF has its calc_p_rho call: step != 0, the damping reads pm1
+    return rc2 == AMT_OK && d->p_rho_per_sweep ? amt_p_rho_domain(who, d, members, 1) : rc2;
 }
 
 namespace {
@@ -354,15 +357,19 @@ int handle_step_t(const char *who, amt_domain *d, int members, bool stacked, int
 
 // Sweeps that are scaffolding (the placement sampling's timed ones): an armed non-finite guard neither checks nor counts them
 // (and does not stretch them), nor does the boundary-zone update follow them, nor a flux accumulation (its counter and
-// accumulators stay as they are).  The settings of the sequence above that such sweeps must not see are saved and restored here.
+// accumulators stay as they are), nor a pressure diagnosis.  The settings of the sequence above that such sweeps must not see are saved and restored here.
 struct StepExtrasPause {
     amt_domain *d;
-    int every, spec_bdy, sumflux_n;
-    explicit StepExtrasPause(amt_domain *dom) : d(dom), every(dom->guard_every), spec_bdy(dom->spec_bdy), sumflux_n(dom->sumflux_n)
+    int every, spec_bdy, sumflux_n, p_rho_per_sweep;
+    explicit StepExtrasPause(amt_domain *dom)
+        : d(dom), every(dom->guard_every), spec_bdy(dom->spec_bdy), sumflux_n(dom->sumflux_n), p_rho_per_sweep(dom->p_rho_per_sweep)
     {
-        d->guard_every = 0; d->spec_bdy = 0; d->sumflux_n = 0;
+        d->guard_every = 0; d->spec_bdy = 0; d->sumflux_n = 0; d->p_rho_per_sweep = 0;
     }
-    ~StepExtrasPause() { d->guard_every = every; d->spec_bdy = spec_bdy; d->sumflux_n = sumflux_n; }
+    ~StepExtrasPause()
+    {
+        d->guard_every = every; d->spec_bdy = spec_bdy; d->sumflux_n = sumflux_n; d->p_rho_per_sweep = p_rho_per_sweep;
+    }
 };
 }  // namespace
 
@@ -443,6 +450,20 @@ int amt_handle_stage_finish(const char *who, amt_domain *d, int members, int n_s
     return amt_stage_finish_domain(who, d, members, n_small_steps, h_diabatic);
 }
 
+// The pressure diagnosis that closes an acoustic sub-step (header section 16).  With per_sweep it is a line of the sweep
+// sequence above (amt_handle_behind_sweep); amt_handle_p_rho is the step = 0 call behind small_step_prep, or any other.  The
+// refusals of amt_p_rho.hip come back before the first device call.
+int amt_handle_set_p_rho(const char *who, amt_domain *d, int members, int mode, int per_sweep, double t0, double smdiv,
+                         void *al, void *p, void *ph, void *pm1, void *alt, void *c2a, void *znu, void *dnw)
+{
+    void *const arr[8] = {al, p, ph, pm1, alt, c2a, znu, dnw};
+    return amt_p_rho_set_domain(who, d, members, mode, per_sweep, t0, smdiv, arr);
+}
+
+void *amt_handle_p_rho_ptr(amt_domain *d, int which) { return which < 0 || which > 7 ? nullptr : d->p_rho_arr[which]; }
+
+int amt_handle_p_rho(const char *who, amt_domain *d, int members, int step) { return amt_p_rho_domain(who, d, members, step); }
+
 extern "C" int amt_domain_cyclic_fill(amt_domain *d, int axes)
 {
     return d ? amt_handle_cyclic_fill("amt_domain_cyclic_fill", d, 1, axes) : amt_null_domain();
@@ -474,6 +495,18 @@ extern "C" int amt_domain_stage_prep(amt_domain *d, int rk_step)
 extern "C" int amt_domain_stage_finish(amt_domain *d, int n_small_steps, const void *h_diabatic)
 {
     return d ? amt_handle_stage_finish("amt_domain_stage_finish", d, 1, n_small_steps, h_diabatic) : amt_null_domain();
+}
+
+extern "C" int amt_domain_set_p_rho(amt_domain *d, int mode, int per_sweep, double t0, double smdiv, void *al, void *p, void *ph,
+                                   void *pm1, void *alt, void *c2a, void *znu, void *dnw)
+{
+    return d ? amt_handle_set_p_rho("amt_domain_set_p_rho", d, 1, mode, per_sweep, t0, smdiv, al, p, ph, pm1, alt, c2a, znu, dnw)
+             : amt_null_domain();
+}
+extern "C" void *amt_domain_p_rho_ptr(amt_domain *d, int which) { return d ? amt_handle_p_rho_ptr(d, which) : nullptr; }
+extern "C" int amt_domain_p_rho(amt_domain *d, int step)
+{
+    return d ? amt_handle_p_rho("amt_domain_p_rho", d, 1, step) : amt_null_domain();
 }
 
 extern "C" int amt_domain_step(amt_domain *d, int n_sweeps)

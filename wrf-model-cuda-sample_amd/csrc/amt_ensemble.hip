@@ -130,6 +130,18 @@ extern "C" int amt_ensemble_stage_finish(amt_ensemble *e, int n_small_steps, con
     return e ? amt_handle_stage_finish("amt_ensemble_stage_finish", &e->d, e->members, n_small_steps, h_diabatic) : amt_null_ensemble();
 }
 
+extern "C" int amt_ensemble_set_p_rho(amt_ensemble *e, int mode, int per_sweep, double t0, double smdiv, void *al, void *p, void *ph,
+                                     void *pm1, void *alt, void *c2a, void *znu, void *dnw)
+{
+    return e ? amt_handle_set_p_rho("amt_ensemble_set_p_rho", &e->d, e->members, mode, per_sweep, t0, smdiv, al, p, ph, pm1, alt, c2a, znu, dnw)
+             : amt_null_ensemble();
+}
+extern "C" void *amt_ensemble_p_rho_ptr(amt_ensemble *e, int which) { return e ? amt_handle_p_rho_ptr(&e->d, which) : nullptr; }
+extern "C" int amt_ensemble_p_rho(amt_ensemble *e, int step)
+{
+    return e ? amt_handle_p_rho("amt_ensemble_p_rho", &e->d, e->members, step) : amt_null_ensemble();
+}
+
 extern "C" int amt_ensemble_step(amt_ensemble *e, int n_sweeps)
 {
     if (!e || n_sweeps < 0) return amt_fail(AMT_ERR_INVALID_ARG, "bad step argument");

@@ -151,6 +151,8 @@ int grid_tile(amt_grid *g, hipStream_t stream, int its, int ite, int jts, int jt
 // and a patch that touches no domain edge enqueues nothing.
 // With amt_domain_set_sumflux the flux accumulation of this rank's own tile follows at the same place:
 // its operands are this rank's u, v and the ww the sweep has just written, nothing is exchanged for it either.
+// With amt_domain_set_p_rho(per_sweep) the pressure diagnosis of this rank's own tile follows the
+// accumulation: it reads the t, mu and muts the sweep has just written in the tile's own columns, nothing is exchanged.
 // The part of a resident handle's sweep sequence behind the sweep (amt_domain.hip), without the guard check: these steppers do
 // not run the non-finite guard.
 int grid_bdy(amt_grid *g, const char *who) { return amt_handle_behind_sweep(who, g->dom, 1); }

@@ -197,6 +197,11 @@ struct amt_domain {
     bool stage_on = false;        // the Runge-Kutta stage bracket is set up (amt_domain_set_stage)
     void *stage_arr[4] = {};      // t_old (3-D), mu_old, mu_save, mub (2-D), times the members of an ensemble
     bool stage_owned = false;     // true: allocated by the library, freed with the setting or the handle
+    int p_rho_mode = 0;           // the pressure diagnosis (amt_domain_set_p_rho): 1 non-hydrostatic, 2 hydrostatic; 0 = off
+    int p_rho_per_sweep = 0;      // 1: one diagnosis with step != 0 follows every sweep
+    double p_rho_t0 = 0., p_rho_smdiv = 0.;
+    void *p_rho_arr[8] = {};      // al, p, ph, pm1, alt, c2a (3-D, times the members of an ensemble), znu, dnw (1-D, shared)
+    bool p_rho_owned = false;     // true: allocated by the library, freed with the setting or the handle
     size_t count(int f) const
     {
         const size_t idim = ime - ims + 1, kdim = kme - kms + 1, jdim = jme - jms + 1;
@@ -248,13 +253,13 @@ void amt_domain_set_shape(amt_domain *d, AMT_SHAPE_SIG);
 //                            holds nothing
 //   amt_handle_close:        releases everything d holds (the caller deletes the handle)
 //   amt_handle_step:         THE SWEEP SEQUENCE of a resident handle, n_sweeps times: guard status, then per sweep
-//                                [cyclic refresh] -> sweep -> [zone update] -> [accumulation] -> [guard check]
+//                                [cyclic refresh] -> sweep -> [zone update] -> [accumulation] -> [pressure diagnosis] -> [guard check]
 //                            stacked = false: the single-patch launch amt_device_call (a domain); true: the launch
 //                            amt_device_call_ensemble (an ensemble, also one of a single member).  A per-sweep setting is a
 //                            member at the END of amt_domain, a line of this sequence, and -- when the placement sampling must
 //                            not see it -- a line of StepExtrasPause next to it.
 //   amt_handle_behind_sweep: the part behind the sweep that the grid and slab steppers share with it (amt_grid.hip): zone update,
-//                            then accumulation; NOT the guard check
+//                            then accumulation, then the pressure diagnosis; NOT the guard check
 //   amt_handle_copy:         device scope, one asynchronous copy between `dev` (inside an array of d) and `host`, stream sync
 //   amt_handle_fill:         the fields of `field_mask` from the generator, member m with seed + m at its offset
 // ---------------------------------------------------------------------------
@@ -277,6 +282,11 @@ int amt_handle_set_stage(const char *who, amt_domain *d, int members, int on, vo
 void *amt_handle_stage_ptr(amt_domain *d, int which);
 int amt_handle_stage_prep(const char *who, amt_domain *d, int members, int rk_step);
 int amt_handle_stage_finish(const char *who, amt_domain *d, int members, int n_small_steps, const void *h_diabatic);
+// the pressure diagnosis that closes an acoustic sub-step (header section 16): a per-sweep setting when per_sweep != 0
+int amt_handle_set_p_rho(const char *who, amt_domain *d, int members, int mode, int per_sweep, double t0, double smdiv,
+                         void *al, void *p, void *ph, void *pm1, void *alt, void *c2a, void *znu, void *dnw);
+void *amt_handle_p_rho_ptr(amt_domain *d, int which);
+int amt_handle_p_rho(const char *who, amt_domain *d, int members, int step);
 int amt_handle_copy(amt_domain *d, void *dev, void *host, size_t bytes, bool up);
 int amt_handle_fill(amt_domain *d, int members, uint64_t field_mask, uint64_t seed,
                     long gi0, long gk0, long gj0, long gidim, long gkdim, long gjdim);
@@ -321,6 +331,19 @@ int amt_stage_prep_domain(const char *who, amt_domain *d, int members, int rk_st
 int amt_stage_finish_domain(const char *who, amt_domain *d, int members, int n_small_steps, const void *h_diabatic);
 int amt_stage_set_domain(const char *who, amt_domain *d, int members, int on, void *t_old, void *mu_old, void *mu_save, void *mub);
 void amt_stage_release(amt_domain *d);
+#pragma GCC visibility pop
+
+// ---------------------------------------------------------------------------
+// the pressure diagnosis calc_p_rho (amt_p_rho.hip, header section 16) of `members` member-stacked patches of the domain's shape
+// on the domain's stream.  The steppers call amt_p_rho_domain only while d->p_rho_per_sweep is set.
+//   amt_p_rho_domain:     one diagnosis; AMT_ERR_PRECONDITION while the setting or the stage bracket (t_old) is off
+//   amt_p_rho_set_domain: amt_*_set_p_rho (mode = 0: off); arr = al, p, ph, pm1, alt, c2a, znu, dnw; a refusal changes nothing
+//   amt_p_rho_release:    turns the setting off and frees what the library allocated
+// ---------------------------------------------------------------------------
+#pragma GCC visibility push(hidden)
+int amt_p_rho_domain(const char *who, amt_domain *d, int members, int step);
+int amt_p_rho_set_domain(const char *who, amt_domain *d, int members, int mode, int per_sweep, double t0, double smdiv, void *const arr[8]);
+void amt_p_rho_release(amt_domain *d);
 #pragma GCC visibility pop
 
 // ---------------------------------------------------------------------------

@@ -9,7 +9,7 @@
 ! domain handle (device arrays kept across calls -- the kernel-only time the
 ! reference reports) and checks that both paths agree bit for bit.
 !
-!   advance_mu_t_driver [NI NK NJ [nsweeps [outdir [flags [placements [members [nsmall [bracket]]]]]]]]
+!   advance_mu_t_driver [NI NK NJ [nsweeps [outdir [flags [placements [members [nsmall [bracket [pressure]]]]]]]]]
 !     flags: 0 none, 1 specified, 2 nested, 3 specified+periodic_x
 !     placements: > 1 samples that many allocations of the resident state and keeps the fastest (amt_domain_tune_placement)
 !     members: > 0 adds an ensemble of that many members of the same shape (amt_ensemble_fill_synthetic, seeds seed + m),
@@ -18,6 +18,8 @@
 !             accumulated on the device behind every sweep (header section 14), on a single patch and on an ensemble
 !     bracket: 1 with nsmall > 0 adds two Runge-Kutta stages on a resident handle whose acoustic loops of nsmall sub-steps run
 !              between small_step_prep and small_step_finish on the device (header section 15); 0 (the default): nothing more
+!     pressure: 1 with nsmall > 0 adds a Runge-Kutta stage whose sub-steps are each closed by calc_p_rho on the device (header
+!              section 16): hydrostatic on a domain handle, non-hydrostatic on an ensemble; 0 (the default): nothing more
 !   With outdir the 7 updated arrays are written there as raw native-endian
 !   streams <name>.bin for an external checker; with members the moments as ens_<field>_<mean|var|lo|hi>.bin:
 !   ww over the whole memory, mu over the compute window, t over the memory less one cell on every side (zero outside).
@@ -46,7 +48,7 @@ program advance_mu_t_driver
   real(c_float) :: ms
   integer(kind=8) :: c0, c1, cmid, hz
   real(kind=8) :: cells, secs
-  integer :: nbad, ndef, ntune, members, nsmall, bracket
+  integer :: nbad, ndef, ntune, members, nsmall, bracket, pressure
   integer(c_int) :: nslots, slot_ids(16)
   real(c_float) :: tune_ms(8)
 
@@ -79,6 +81,10 @@ program advance_mu_t_driver
   bracket = 0
   if (command_argument_count() >= 10) then
      call get_command_argument(10, arg); read (arg, *) bracket
+  end if
+  pressure = 0
+  if (command_argument_count() >= 11) then
+     call get_command_argument(11, arg); read (arg, *) pressure
   end if
   config_flags%specified  = (iflag == 1 .or. iflag == 3)
   config_flags%nested     = (iflag == 2)
@@ -285,8 +291,125 @@ program advance_mu_t_driver
   if (members > 0) call ensemble_moments()
   if (nsmall > 0) call flux_averages()
   if (nsmall > 0 .and. bracket == 1) call stage_bracket()
+  if (nsmall > 0 .and. pressure == 1) call pressure_diagnosis()
 
 contains
+
+  ! One Runge-Kutta stage whose acoustic loop of nsmall sub-steps runs with calc_p_rho on the device: step 0 behind
+  ! small_step_prep, then one diagnosis behind every sweep (per_sweep).  The stage bracket's four arrays are fields of a second
+  ! handle as in stage_bracket; al, p, ph, pm1, alt, c2a, znu, dnw are fields of a third one (ww, ww_1, u, u_1, v, v_1, fnm, dnw;
+  ! filled from the generator, they come down with amt_domain_download).  Hydrostatic (mode 2) on the domain handle, where the
+  ! pointer-level call repeats the step-0 diagnosis and must give the same bits; non-hydrostatic (mode 1) on an ensemble.
+  subroutine pressure_diagnosis()
+    type(c_ptr) :: d, ex, px, own, e, eex, epx
+    real(wp), allocatable, target :: a3(:,:,:), b3(:,:,:)
+    integer(c_int) :: wb, mm, k
+    integer(c_int), parameter :: xf(4) = [AMT_F_T, AMT_F_MU, AMT_F_MUAVE, AMT_F_MUT]      ! of `ex`: t_old, mu_old, mu_save, mub
+    ! of `px`: al, p, ph, pm1, alt, c2a, znu, dnw
+    integer(c_int), parameter :: pf(8) = [AMT_F_WW, AMT_F_WW_1, AMT_F_U, AMT_F_U_1, AMT_F_V, AMT_F_V_1, AMT_F_FNM, AMT_F_DNW]
+    real(c_double), parameter :: t0 = 300.0_c_double, smdiv = 0.1_c_double
+    wb = int(storage_size(rdx)/8, c_int)
+    mm = int(max(members, 1), c_int)
+    allocate (a3(ims:ime,kms:kme,jms:jme), b3(ims:ime,kms:kme,jms:jme))
+    call make_domain(d, seed)
+    call make_domain(ex, seed + 1_c_int64_t)
+    call make_domain(px, seed + 2_c_int64_t)
+    call make_domain(own, seed)
+    ! off until set; the setting needs the stage bracket; a mix of given and missing arrays is refused
+    if (c_associated(amt_domain_p_rho_ptr(d, 0_c_int))) error stop 10
+    if (amt_domain_p_rho(d, 0_c_int) /= AMT_ERR_PRECONDITION) error stop 10
+    if (amt_domain_set_p_rho(d, 2_c_int, 1_c_int, t0, smdiv, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr,     &
+                             c_null_ptr, c_null_ptr, c_null_ptr) /= AMT_ERR_PRECONDITION) error stop 10
+    call amt_check(amt_domain_set_stage(d, 1_c_int, amt_domain_field_ptr(ex, xf(1)), amt_domain_field_ptr(ex, xf(2)),       &
+                   amt_domain_field_ptr(ex, xf(3)), amt_domain_field_ptr(ex, xf(4))), 'amt_domain_set_stage')
+    if (amt_domain_set_p_rho(d, 2_c_int, 1_c_int, t0, smdiv, amt_domain_field_ptr(px, pf(1)), c_null_ptr, c_null_ptr,       &
+                             c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr) /= AMT_ERR_INVALID_ARG) error stop 10
+    call amt_check(amt_domain_set_p_rho(d, 2_c_int, 1_c_int, t0, smdiv, amt_domain_field_ptr(px, pf(1)),                    &
+                   amt_domain_field_ptr(px, pf(2)), amt_domain_field_ptr(px, pf(3)), amt_domain_field_ptr(px, pf(4)),       &
+                   amt_domain_field_ptr(px, pf(5)), amt_domain_field_ptr(px, pf(6)), amt_domain_field_ptr(px, pf(7)),       &
+                   amt_domain_field_ptr(px, pf(8))), 'amt_domain_set_p_rho')
+    if (.not. c_associated(amt_domain_p_rho_ptr(d, 7_c_int), amt_domain_field_ptr(px, pf(8)))) error stop 10
+    ! the library's own eight arrays on another handle: allocated, named, freed
+    call amt_check(amt_domain_set_stage(own, 1_c_int, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr), 'amt_domain_set_stage')
+    call amt_check(amt_domain_set_p_rho(own, 1_c_int, 0_c_int, t0, smdiv, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr,   &
+                   c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr), 'amt_domain_set_p_rho')
+    do k = 0, 7
+       if (.not. c_associated(amt_domain_p_rho_ptr(own, k))) error stop 10
+    end do
+    call amt_check(amt_domain_set_p_rho(own, 0_c_int, 0_c_int, t0, smdiv, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr,   &
+                   c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr), 'amt_domain_set_p_rho')
+    if (c_associated(amt_domain_p_rho_ptr(own, 0_c_int))) error stop 10
+    call amt_check(amt_domain_destroy(own), 'amt_domain_destroy')
+    ! the stage: prep, the step-0 diagnosis -- by the handle, then once more by the pointer-level call: the same bits --, the
+    ! sub-steps with one diagnosis behind each, finish
+    call amt_check(amt_domain_stage_prep(d, 1_c_int), 'amt_domain_stage_prep')
+    call amt_check(amt_domain_p_rho(d, 0_c_int), 'amt_domain_p_rho')
+    call amt_check(amt_domain_download(px, pf(2), c_loc(a3)), 'amt_domain_download')
+    call p_rho_device(d, ex, px)
+    call amt_check(amt_domain_sync(d), 'amt_domain_sync')
+    call amt_check(amt_domain_download(px, pf(2), c_loc(b3)), 'amt_domain_download')
+    if (any(transfer(a3, 1_c_int8_t, size(a3) * wb) /= transfer(b3, 1_c_int8_t, size(b3) * wb))) error stop 11
+    call amt_check(amt_domain_step(d, int(nsmall, c_int)), 'amt_domain_step')
+    call amt_check(amt_domain_stage_finish(d, int(nsmall, c_int), c_null_ptr), 'amt_domain_stage_finish')
+    call amt_check(amt_domain_sync(d), 'amt_domain_sync')
+    call amt_check(amt_domain_download(px, pf(2), c_loc(a3)), 'amt_domain_download')
+    if (len_trim(outdir) > 0) call dump3('p_rho_p', a3)
+    ! an ensemble, non-hydrostatic: every member's diagnosis in one launch, the arrays member-stacked in two more ensembles
+    call make_ensemble(e, mm, seed)
+    call make_ensemble(eex, mm, seed + 1_c_int64_t)
+    call make_ensemble(epx, mm, seed + 2_c_int64_t)
+    call amt_check(amt_ensemble_set_stage(e, 1_c_int, amt_ensemble_field_ptr(eex, xf(1)), amt_ensemble_field_ptr(eex, xf(2)),  &
+                   amt_ensemble_field_ptr(eex, xf(3)), amt_ensemble_field_ptr(eex, xf(4))), 'amt_ensemble_set_stage')
+    call amt_check(amt_ensemble_set_p_rho(e, 1_c_int, 1_c_int, t0, smdiv, amt_ensemble_field_ptr(epx, pf(1)),               &
+                   amt_ensemble_field_ptr(epx, pf(2)), amt_ensemble_field_ptr(epx, pf(3)), amt_ensemble_field_ptr(epx, pf(4)), &
+                   amt_ensemble_field_ptr(epx, pf(5)), amt_ensemble_field_ptr(epx, pf(6)), amt_ensemble_field_ptr(epx, pf(7)), &
+                   amt_ensemble_field_ptr(epx, pf(8))), 'amt_ensemble_set_p_rho')
+    if (.not. c_associated(amt_ensemble_p_rho_ptr(e, 1_c_int), amt_ensemble_field_ptr(epx, pf(2)))) error stop 10
+    call amt_check(amt_ensemble_stage_prep(e, 1_c_int), 'amt_ensemble_stage_prep')
+    call amt_check(amt_ensemble_p_rho(e, 0_c_int), 'amt_ensemble_p_rho')
+    call amt_check(amt_ensemble_step(e, int(nsmall, c_int)), 'amt_ensemble_step')
+    call amt_check(amt_ensemble_stage_finish(e, int(nsmall, c_int), c_null_ptr), 'amt_ensemble_stage_finish')
+    call amt_check(amt_ensemble_sync(e), 'amt_ensemble_sync')
+    print '(a,i0,a,i0,a,es24.16)', 'calc_p_rho behind each of ', nsmall, ' sub-steps on the device, hydrostatic on a domain and '// &
+       'non-hydrostatic on an ensemble of ', mm, ' members; checksum of p: ', sum(real(a3(its:ite-1, kts:kte-1, jts:jte-1), 8))
+    call amt_check(amt_ensemble_destroy(e), 'amt_ensemble_destroy')
+    call amt_check(amt_ensemble_destroy(eex), 'amt_ensemble_destroy')
+    call amt_check(amt_ensemble_destroy(epx), 'amt_ensemble_destroy')
+    call amt_check(amt_domain_set_p_rho(d, 0_c_int, 0_c_int, t0, smdiv, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr,     &
+                   c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr), 'amt_domain_set_p_rho')
+    call amt_check(amt_domain_destroy(d), 'amt_domain_destroy')
+    call amt_check(amt_domain_destroy(ex), 'amt_domain_destroy')
+    call amt_check(amt_domain_destroy(px), 'amt_domain_destroy')
+  end subroutine
+
+  ! the step-0 diagnosis of handle h, hydrostatic, with the pointer-level call on h's stream: t_old of `ex`, the eight of `px`
+  subroutine p_rho_device(h, ex, px)
+    type(c_ptr), intent(in) :: h, ex, px
+    type(c_ptr) :: stream
+    stream = amt_domain_stream(h)
+    if (storage_size(rdx) == 64) then
+       rc = amt_p_rho_device_f64(stream, 1_c_int, 2_c_int, 0_c_int, amt_domain_field_ptr(px, AMT_F_WW),                      &
+                                 amt_domain_field_ptr(px, AMT_F_WW_1), amt_domain_field_ptr(px, AMT_F_U),                   &
+                                 amt_domain_field_ptr(px, AMT_F_U_1), amt_domain_field_ptr(px, AMT_F_V),                    &
+                                 amt_domain_field_ptr(px, AMT_F_V_1), amt_domain_field_ptr(h, AMT_F_T),                     &
+                                 amt_domain_field_ptr(ex, AMT_F_T), amt_domain_field_ptr(h, AMT_F_MU),                      &
+                                 amt_domain_field_ptr(h, AMT_F_MUTS), amt_domain_field_ptr(h, AMT_F_RDNW),                  &
+                                 amt_domain_field_ptr(px, AMT_F_FNM), amt_domain_field_ptr(px, AMT_F_DNW),                  &
+                                 300.0_c_double, 0.1_c_double,                                                              &
+                                 ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte)
+    else
+       rc = amt_p_rho_device_f32(stream, 1_c_int, 2_c_int, 0_c_int, amt_domain_field_ptr(px, AMT_F_WW),                      &
+                                 amt_domain_field_ptr(px, AMT_F_WW_1), amt_domain_field_ptr(px, AMT_F_U),                   &
+                                 amt_domain_field_ptr(px, AMT_F_U_1), amt_domain_field_ptr(px, AMT_F_V),                    &
+                                 amt_domain_field_ptr(px, AMT_F_V_1), amt_domain_field_ptr(h, AMT_F_T),                     &
+                                 amt_domain_field_ptr(ex, AMT_F_T), amt_domain_field_ptr(h, AMT_F_MU),                      &
+                                 amt_domain_field_ptr(h, AMT_F_MUTS), amt_domain_field_ptr(h, AMT_F_RDNW),                  &
+                                 amt_domain_field_ptr(px, AMT_F_FNM), amt_domain_field_ptr(px, AMT_F_DNW),                  &
+                                 300.0_c_float, 0.1_c_float,                                                                &
+                                 ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte)
+    end if
+    call amt_check(rc, 'amt_p_rho_device')
+  end subroutine
 
   ! Two Runge-Kutta stages (rk_step 1 without, rk_step 2 with a diabatic heating) whose acoustic loops of nsmall sub-steps run
   ! between small_step_prep and small_step_finish on the device.  t_old, mu_old, mu_save, mub and h_diabatic are the caller's:

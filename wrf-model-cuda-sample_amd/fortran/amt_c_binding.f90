@@ -1210,6 +1210,79 @@ MODULE amt_c_binding
          type(c_ptr), value :: h_diabatic                                            ! device pointer or c_null_ptr
          integer(c_int) :: rc
       end function
+      ! (16) the pressure diagnosis that closes an acoustic sub-step: calc_p_rho.  Pointer level (members = 1 for a single
+      ! patch): every array is a DEVICE pointer; asynchronous on hip_stream.  mode 1 non-hydrostatic (ph is read), 2 hydrostatic
+      ! (ph is integrated up the column); step 0 behind small_step_prep, step /= 0 behind a sub-step (p is damped against pm1)
+      function amt_p_rho_device_f32(hip_stream, members, mode, step, al, p, ph, pm1, alt, c2a, t, t_old, mu, muts, rdnw,  &
+                                    znu, dnw, t0, smdiv, ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,           &
+                                    its, ite, jts, jte, kts, kte) bind(C, name="amt_p_rho_device_f32") result(rc)
+         import :: c_ptr, c_int, c_float
+         type(c_ptr), value :: hip_stream
+         integer(c_int), value :: members, mode, step
+         type(c_ptr), value :: al, p, ph, pm1, alt, c2a, t, t_old, mu, muts, rdnw, znu, dnw               ! device pointers
+         real(c_float), value :: t0, smdiv
+         integer(c_int), value :: ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme
+         integer(c_int), value :: its, ite, jts, jte, kts, kte
+         integer(c_int) :: rc
+      end function
+      function amt_p_rho_device_f64(hip_stream, members, mode, step, al, p, ph, pm1, alt, c2a, t, t_old, mu, muts, rdnw,  &
+                                    znu, dnw, t0, smdiv, ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,           &
+                                    its, ite, jts, jte, kts, kte) bind(C, name="amt_p_rho_device_f64") result(rc)
+         import :: c_ptr, c_int, c_double
+         type(c_ptr), value :: hip_stream
+         integer(c_int), value :: members, mode, step
+         type(c_ptr), value :: al, p, ph, pm1, alt, c2a, t, t_old, mu, muts, rdnw, znu, dnw               ! device pointers
+         real(c_double), value :: t0, smdiv
+         integer(c_int), value :: ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme
+         integer(c_int), value :: its, ite, jts, jte, kts, kte
+         integer(c_int) :: rc
+      end function
+      ! set: mode = 0 off (the default); mode = 1 or 2 with eight c_null_ptr: the library allocates al, p, ph, pm1, alt, c2a, znu,
+      ! dnw (the host fills alt, c2a, ph, znu, dnw through amt_domain_p_rho_ptr), with eight device pointers: the caller's.  It
+      ! needs amt_domain_set_stage.  per_sweep /= 0: one diagnosis follows every sweep of amt_domain_step, amt_slab_step,
+      ! amt_grid_step ...; amt_domain_p_rho runs one now (step = 0 behind amt_domain_stage_prep)
+      function amt_domain_set_p_rho(handle, mode, per_sweep, t0, smdiv, al, p, ph, pm1, alt, c2a, znu, dnw)                   &
+                                    bind(C, name="amt_domain_set_p_rho") result(rc)
+         import :: c_ptr, c_int, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: mode, per_sweep
+         real(c_double), value :: t0, smdiv
+         type(c_ptr), value :: al, p, ph, pm1, alt, c2a, znu, dnw
+         integer(c_int) :: rc
+      end function
+      function amt_domain_p_rho_ptr(handle, which) bind(C, name="amt_domain_p_rho_ptr") result(ptr)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: which                         ! 0 al, 1 p, 2 ph, 3 pm1, 4 alt, 5 c2a, 6 znu, 7 dnw
+         type(c_ptr) :: ptr
+      end function
+      function amt_domain_p_rho(handle, step) bind(C, name="amt_domain_p_rho") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: step
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_set_p_rho(handle, mode, per_sweep, t0, smdiv, al, p, ph, pm1, alt, c2a, znu, dnw)                   &
+                                    bind(C, name="amt_ensemble_set_p_rho") result(rc)
+         import :: c_ptr, c_int, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: mode, per_sweep
+         real(c_double), value :: t0, smdiv
+         type(c_ptr), value :: al, p, ph, pm1, alt, c2a, znu, dnw
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_p_rho_ptr(handle, which) bind(C, name="amt_ensemble_p_rho_ptr") result(ptr)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: which                         ! 0 al, 1 p, 2 ph, 3 pm1, 4 alt, 5 c2a, 6 znu, 7 dnw
+         type(c_ptr) :: ptr
+      end function
+      function amt_ensemble_p_rho(handle, step) bind(C, name="amt_ensemble_p_rho") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: step
+         integer(c_int) :: rc
+      end function
    end interface
 
    ! enum amt_field (include/amt_synth.h): the Fortran argument order

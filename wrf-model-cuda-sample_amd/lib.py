@@ -224,6 +224,14 @@ SYMBOLS = {
     "amt_ensemble_stage_ptr": (_P, [_P, _I]),
     "amt_ensemble_stage_prep": (_I, [_P, _I]),
     "amt_ensemble_stage_finish": (_I, [_P, _I, _P]),
+    "amt_p_rho_device_f32": (_I, [_P, _I, _I, _I] + [_P] * 13 + [ctypes.c_float] * 2 + [_I] * 17),
+    "amt_p_rho_device_f64": (_I, [_P, _I, _I, _I] + [_P] * 13 + [ctypes.c_double] * 2 + [_I] * 17),
+    "amt_domain_set_p_rho": (_I, [_P, _I, _I, ctypes.c_double, ctypes.c_double] + [_P] * 8),
+    "amt_domain_p_rho_ptr": (_P, [_P, _I]),
+    "amt_domain_p_rho": (_I, [_P, _I]),
+    "amt_ensemble_set_p_rho": (_I, [_P, _I, _I, ctypes.c_double, ctypes.c_double] + [_P] * 8),
+    "amt_ensemble_p_rho_ptr": (_P, [_P, _I]),
+    "amt_ensemble_p_rho": (_I, [_P, _I]),
     "amt_halo_plan": (_I, [_I] * (4 + 17 + 5) + [ctypes.POINTER(HaloMessage), _I, ctypes.POINTER(_I)]),
     "amt_grid_halo_messages": (_I, [_P, ctypes.POINTER(HaloMessage), _I, ctypes.POINTER(_I)]),
     "amt_slab_halo_messages": (_I, [_P, ctypes.POINTER(HaloMessage), _I, ctypes.POINTER(_I)]),
@@ -289,7 +297,7 @@ class DeviceView:
 
 
 class ResidentHandle:
-    """What a resident handle does whichever kind it is (header sections 4, 8, 9, 10, 12, 14, 15): stepping, the per-sweep settings,
+    """What a resident handle does whichever kind it is (header sections 4, 8, 9, 10, 12, 14, 15, 16): stepping, the per-sweep settings,
     the diagnostics and the release.  The owning class names its C functions' prefix (``amt_domain`` / ``amt_ensemble``) in
     ``_PREFIX`` and its member count in ``_members()``, and holds the library in ``L`` and the handle in ``handle``.  The stepping
     methods pass their status through ``_check`` so that an ERR_NONFINITE error carries the guard's report."""
@@ -435,6 +443,26 @@ class ResidentHandle:
         """``stage_finish``: small_step_finish behind a loop of ``n_small_steps`` sweeps, with the handle's dts;
         ``h_diabatic``: a device tensor (or address) of one 3-D field's extents, or None."""
         check(self._fn("stage_finish")(self.handle, int(n_small_steps), _address(h_diabatic)))
+
+    # the pressure diagnosis that closes an acoustic sub-step: calc_p_rho (header section 16)
+    def set_p_rho(self, mode: int, per_sweep: bool = False, t0: float = 300.0, smdiv: float = 0.0,
+                  al=None, p=None, ph=None, pm1=None, alt=None, c2a=None, znu=None, dnw=None) -> None:
+        """``set_p_rho``: mode 0 = off, 1 = non-hydrostatic, 2 = hydrostatic.  Without arrays the library allocates ``al``, ``p``,
+        ``ph``, ``pm1``, ``alt``, ``c2a`` (one 3-D field's extents times the members) and ``znu``, ``dnw`` (one level array);
+        otherwise all eight are device tensors (or addresses) which the caller keeps alive.  ``alt``, ``c2a``, ``ph``, ``znu``,
+        ``dnw`` are the host's to fill (``p_rho_ptr``).  Needs ``set_stage``.  ``per_sweep``: every sweep of ``step`` is followed
+        by one diagnosis with step != 0."""
+        check(self._fn("set_p_rho")(self.handle, int(mode), int(bool(per_sweep)), float(t0), float(smdiv),
+                                    *[_address(a) for a in (al, p, ph, pm1, alt, c2a, znu, dnw)]))
+
+    def p_rho_ptr(self, which: int) -> int:
+        """Device address of al (0), p (1), ph (2), pm1 (3), alt (4), c2a (5), znu (6) or dnw (7); 0 while the setting is off."""
+        return int(self._fn("p_rho_ptr")(self.handle, int(which)) or 0)
+
+    def p_rho(self, step: int) -> None:
+        """``p_rho``: one diagnosis now, asynchronous on the handle's stream (every member of an ensemble in one launch);
+        ``step`` 0 is the call behind ``stage_prep``."""
+        check(self._fn("p_rho")(self.handle, int(step)))
 
 
 def _address(a):

@@ -518,6 +518,35 @@ class _NativeStepper:
         with self._dev():
             self._lib.check(self.L.amt_domain_stage_finish(self._dom, int(n_small_steps), self._lib._address(h_diabatic)))
 
+    # The pressure diagnosis that closes an acoustic sub-step (header section 16) on this rank's own tile; it needs
+    # ``set_stage``.  With ``per_sweep`` the stepper's step calls enqueue it where the flux accumulation is; nothing is exchanged.
+    def set_p_rho(self, mode: int, per_sweep: bool = False, t0: float = 300.0, smdiv: float = 0.0):
+        """The library allocates al, p, ph, pm1, alt, c2a, znu, dnw (``p_rho_arrays``); mode 0 frees them."""
+        with self._dev():
+            self._lib.check(self.L.amt_domain_set_p_rho(self._dom, int(mode), int(bool(per_sweep)), float(t0), float(smdiv),
+                                                        *[None] * 8))
+
+    def p_rho_ptr(self, which: int) -> int:
+        return int(self.L.amt_domain_p_rho_ptr(self._dom, int(which)) or 0)
+
+    def p_rho_arrays(self):
+        """al, p, ph, pm1, alt, c2a, znu, dnw as torch tensors that view the library's device arrays (valid while the stepper
+        lives)."""
+        import torch
+        b, t0 = self.patch.bounds, self.patch.arrays["t_1"]
+        out = []
+        for which in range(8):
+            ptr = self.L.amt_domain_p_rho_ptr(self._dom, which)
+            if not ptr:
+                raise self._lib.AmtError(self._lib.ERR_PRECONDITION, "the pressure diagnosis is off")
+            view = self._lib.DeviceView(self, ptr, b.shape("t" if which < 6 else "dnw"), "<f8" if t0.element_size() == 8 else "<f4")
+            out.append(torch.as_tensor(view, device=t0.device))
+        return tuple(out)
+
+    def p_rho(self, step: int):
+        with self._dev():
+            self._lib.check(self.L.amt_domain_p_rho(self._dom, int(step)))
+
     def close(self):
         if self._h:
             with self._dev():
