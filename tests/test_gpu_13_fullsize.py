@@ -21,7 +21,11 @@ pytestmark = pytest.mark.gpu
 
 
 def _host_gb():
-    """Host memory this process may really use, GB: MemAvailable, capped by the cgroup's memory.max."""
+    """Host memory this process may really use, GB: MemAvailable, capped by the cgroup's memory.max less what the cgroup
+    holds and cannot give back.  memory.current counts the page cache of every file the cgroup has read or written -- the
+    libraries, a build, earlier tests' files --, which the kernel drops under pressure exactly as it does the cache that
+    MemAvailable already counts as available: it is taken out of `used` (active_file + inactive_file of memory.stat; shmem is
+    not among them and stays counted)."""
     avail = 0.0
     try:
         with open("/proc/meminfo") as f:
@@ -38,6 +42,12 @@ def _host_gb():
             try:
                 with open("/sys/fs/cgroup/memory.current") as g:
                     used = int(g.read().strip())
+            except (OSError, ValueError):
+                pass
+            try:
+                with open("/sys/fs/cgroup/memory.stat") as g:
+                    stat = dict(line.split() for line in g if len(line.split()) == 2)
+                used = max(0, used - int(stat.get("active_file", 0)) - int(stat.get("inactive_file", 0)))
             except (OSError, ValueError):
                 pass
             avail = min(avail, (int(v) - used) / 1e9)
