@@ -308,12 +308,22 @@ int amt_bdy_update_domain(const char *who, amt_domain *d, int members);
 int amt_bdy_check_domain(const char *who, const amt_domain *d, int members);
 
 // ---------------------------------------------------------------------------
+// The three streaming passes around the acoustic loop -- the flux averages, the stage bracket, the pressure diagnosis -- have
+// their kernels, their scalar arguments and what their setting means in a file each; the check of a call, the layout of the
+// tile box, the way from the check to the launch, the setting of a handle's arrays (all or none, the library's own handed
+// back, the probe check, allocation, release) and the bounds of the pointer-level exports are amt_pass.h / amt_pass.hip.
+// Each *_set_domain is amt_*_set_<pass>: a refusal changes nothing; each *_release turns the setting off and frees what the
+// library allocated (the handles' destroy).
+// ---------------------------------------------------------------------------
+#include "amt_pass.h"
+
+// ---------------------------------------------------------------------------
 // the acoustic loop's flux averages (amt_sumflux.hip, header section 14).  The steppers call amt_sumflux_accumulate_domain
 // only while the setting is on (d->sumflux_n != 0): with it off they enqueue what they always did.
 //   amt_sumflux_accumulate_domain: one accumulation of `members` member-stacked patches of the domain's shape on the domain's
-//                                  stream, as iteration d->sumflux_next, which then advances 1..n and wraps
-//   amt_sumflux_set_domain:        amt_*_set_sumflux (n = 0: off); a refusal changes nothing
-//   amt_sumflux_release:           turns the setting off and frees what the library allocated (the handles' destroy)
+//                                  stream, as iteration d->sumflux_next, which then advances 1..n and wraps;
+//                                  AMT_ERR_INVALID_ARG while the setting is off
+//   amt_sumflux_set_domain:        n = 0: off; the library's own arrays handed back: n and the counter are set anew
 // ---------------------------------------------------------------------------
 int amt_sumflux_accumulate_domain(const char *who, amt_domain *d, int members);
 int amt_sumflux_set_domain(const char *who, amt_domain *d, int members, int n, void *ru_m, void *rv_m, void *ww_m);
@@ -323,8 +333,7 @@ void amt_sumflux_release(amt_domain *d);
 // the bracket of a Runge-Kutta stage (amt_stage.hip, header section 15): small_step_prep and small_step_finish of `members`
 // member-stacked patches of the domain's shape on the domain's stream.  Nothing of the sweep sequence calls these.
 //   amt_stage_prep_domain / amt_stage_finish_domain: AMT_ERR_PRECONDITION while the setting is off; finish uses the domain's dts
-//   amt_stage_set_domain:                            amt_*_set_stage (on = 0: off); a refusal changes nothing
-//   amt_stage_release:                               turns the setting off and frees what the library allocated
+//   amt_stage_set_domain:                            on = 0: off; the library's own arrays handed back: nothing changes
 // ---------------------------------------------------------------------------
 #pragma GCC visibility push(hidden)
 int amt_stage_prep_domain(const char *who, amt_domain *d, int members, int rk_step);
@@ -337,8 +346,8 @@ void amt_stage_release(amt_domain *d);
 // the pressure diagnosis calc_p_rho (amt_p_rho.hip, header section 16) of `members` member-stacked patches of the domain's shape
 // on the domain's stream.  The steppers call amt_p_rho_domain only while d->p_rho_per_sweep is set.
 //   amt_p_rho_domain:     one diagnosis; AMT_ERR_PRECONDITION while the setting or the stage bracket (t_old) is off
-//   amt_p_rho_set_domain: amt_*_set_p_rho (mode = 0: off); arr = al, p, ph, pm1, alt, c2a, znu, dnw; a refusal changes nothing
-//   amt_p_rho_release:    turns the setting off and frees what the library allocated
+//   amt_p_rho_set_domain: mode = 0: off; arr = al, p, ph, pm1, alt, c2a, znu, dnw; AMT_ERR_PRECONDITION while the stage bracket
+//                         is off; the library's own arrays handed back: the mode and the scalars are set anew
 // ---------------------------------------------------------------------------
 #pragma GCC visibility push(hidden)
 int amt_p_rho_domain(const char *who, amt_domain *d, int members, int step);

@@ -241,44 +241,17 @@ __global__ __launch_bounds__(256) void amt_stage_finish_kernel(AmtStageJobs<T> j
     }
 }
 
-// One array of a call, for the checks: outputs may overlap nothing, inputs may alias one another.
-struct StageArray {
-    const void *p;
-    bool three_d, output, optional;
-};
+// a tile with one level holds cells of ww and the columns of mu; one without a mass column holds nothing
+const AmtPassRules kStageRules = {1, true, "an output array overlaps another array of the call", "an output array overlaps another array of the call"};
 
-// Argument and precondition checks: host arithmetic only.  *empty: the range holds no column (nothing to do).
-int stage_check(const char *who, const amt_domain &s, int members, const StageArray *arr, int narr, const char *count_name, int count,
+// Argument and precondition checks (amt_pass.h): host arithmetic only.  *empty: the range holds no column (nothing to do).
+int stage_check(const char *who, const amt_domain &s, int members, const AmtPassArray *arr, int narr, const char *count_name, int count,
                 bool *empty)
 {
-    *empty = false;
-    for (int k = 0; k < narr; ++k)
-        if (!arr[k].p && !arr[k].optional) return amt_fail(AMT_ERR_INVALID_ARG, "%s: null array pointer", who);
-    if (members < 1) return amt_fail(AMT_ERR_INVALID_ARG, "%s: members = %d: an ensemble has at least one member", who, members);
+    const int rc = amt_pass_check_arrays(who, members, arr, narr);
+    if (rc) return rc;
     if (count < 1) return amt_fail(AMT_ERR_INVALID_ARG, "%s: %s = %d: at least 1", who, count_name, count);
-    if (s.ime < s.ims || s.jme < s.jms || s.kme < s.kms) return amt_fail(AMT_ERR_PRECONDITION, "%s: empty memory extents", who);
-    const size_t idim = s.ime - s.ims + 1, kdim = s.kme - s.kms + 1, jdim = s.jme - s.jms + 1;
-    const size_t b3 = idim * kdim * jdim * (size_t)members * (size_t)s.dtype_bytes, b2 = idim * jdim * (size_t)members * (size_t)s.dtype_bytes;
-    for (int k = 0; k < narr; ++k) {
-        if (!arr[k].p) continue;
-        const uintptr_t p0 = reinterpret_cast<uintptr_t>(arr[k].p), pb = arr[k].three_d ? b3 : b2;
-        for (int m = k + 1; m < narr; ++m) {
-            if (!arr[m].p || !(arr[k].output || arr[m].output)) continue;
-            const uintptr_t r0 = reinterpret_cast<uintptr_t>(arr[m].p), rb = arr[m].three_d ? b3 : b2;
-            if (p0 < r0 + rb && r0 < p0 + pb) return amt_fail(AMT_ERR_INVALID_ARG, "%s: an output array overlaps another array of the call", who);
-        }
-    }
-    if (s.kts != 1) return amt_fail(AMT_ERR_PRECONDITION, "%s: kts = %d, the library needs kts == 1", who, s.kts);
-    if (s.kte != s.kde) return amt_fail(AMT_ERR_PRECONDITION, "%s: kte = %d is not kde = %d", who, s.kte, s.kde);
-    if (s.kme < s.kte || s.kms > s.kts) return amt_fail(AMT_ERR_PRECONDITION, "%s: levels kts:kte = %d:%d are not inside memory kms:kme = %d:%d", who, s.kts, s.kte, s.kms, s.kme);
-    if (s.ite < s.its || s.jte < s.jts || s.kte < s.kts) { *empty = true; return AMT_OK; }
-    if (s.its < s.ims || s.ite > s.ime || s.jts < s.jms || s.jte > s.jme)
-        return amt_fail(AMT_ERR_PRECONDITION, "%s: the tile %d:%d, %d:%d is not inside memory %d:%d, %d:%d", who,
-                        s.its, s.ite, s.jts, s.jte, s.ims, s.ime, s.jms, s.jme);
-    if (members > 65535) return amt_fail(AMT_ERR_PRECONDITION, "%s: %d members: one launch covers at most 65535", who, members);
-    const int ihi = s.ite < s.ide - 1 ? s.ite : s.ide - 1, jhi = s.jte < s.jde - 1 ? s.jte : s.jde - 1;
-    if (ihi < s.its || jhi < s.jts) *empty = true;
-    return AMT_OK;
+    return amt_pass_check_box(who, s, members, arr, narr, kStageRules, empty);
 }
 
 struct StagePrepArrays {
@@ -300,39 +273,27 @@ int stage_prep_check(const char *who, const amt_domain &d, int members, const St
 {
     const bool first = rk_step == 1;
     // mudf at rk_step > 1 is neither read nor written: it takes no part in the checks
-    const StageArray arr[12] = {{a.t, true, true, false}, {a.t_1, true, true, false}, {a.t_old, true, first, false},
-                                {a.ww, true, false, false}, {a.ww_1, true, true, false}, {a.mu, false, true, false},
-                                {a.mu_old, false, first, false}, {a.mu_save, false, true, false}, {a.muts, false, true, false},
-                                {first ? a.mudf : nullptr, false, true, !first}, {a.mut, false, false, false}, {a.mub, false, false, false}};
+    const AmtPassArray arr[12] = {{a.t, 3, true, false}, {a.t_1, 3, true, false}, {a.t_old, 3, first, false},
+                                  {a.ww, 3, false, false}, {a.ww_1, 3, true, false}, {a.mu, 2, true, false},
+                                  {a.mu_old, 2, first, false}, {a.mu_save, 2, true, false}, {a.muts, 2, true, false},
+                                  {first ? a.mudf : nullptr, 2, true, !first}, {a.mut, 2, false, false}, {a.mub, 2, false, false}};
     return stage_check(who, d, members, arr, 12, "rk_step", rk_step, empty);
 }
 
 int stage_finish_check(const char *who, const amt_domain &d, int members, const StageFinishArrays &a, int n, bool *empty)
 {
-    const StageArray arr[9] = {{a.t, true, true, false}, {a.t_1, true, false, false}, {a.ww, true, true, false},
-                               {a.ww_1, true, false, false}, {a.mu, false, true, false}, {a.mu_save, false, false, false},
-                               {a.muts, false, false, false}, {a.mut, false, false, false}, {a.h, true, false, true}};
+    const AmtPassArray arr[9] = {{a.t, 3, true, false}, {a.t_1, 3, false, false}, {a.ww, 3, true, false},
+                                 {a.ww_1, 3, false, false}, {a.mu, 2, true, false}, {a.mu_save, 2, false, false},
+                                 {a.muts, 2, false, false}, {a.mut, 2, false, false}, {a.h, 3, false, true}};
     return stage_check(who, d, members, arr, 9, "n_small_steps", n, empty);
 }
 
 template <typename T>
 void stage_box(const amt_domain &d, AmtStageJobs<T> &jobs)
 {
-    const long idim = d.ime - d.ims + 1, kdim = d.kme - d.kms + 1, jdim = d.jme - d.jms + 1;
-    jobs.ni = (d.ite < d.ide - 1 ? d.ite : d.ide - 1) - d.its + 1;
+    amt_pass_mass_lengths(d, &jobs.ni, &jobs.nj);
     jobs.nk = d.kte - d.kts + 1;
-    jobs.nj = (d.jte < d.jde - 1 ? d.jte : d.jde - 1) - d.jts + 1;
-    jobs.idim = idim; jobs.jstride3 = kdim * idim; jobs.mstride3 = idim * kdim * jdim; jobs.mstride2 = idim * jdim;
-    jobs.first3 = ((long)(d.jts - d.jms) * kdim + (d.kts - d.kms)) * idim + (d.its - d.ims);
-    jobs.first2 = (long)(d.jts - d.jms) * idim + (d.its - d.ims);
-}
-
-// blocks of 256 threads for `total` work items: as many as amt_sumflux.hip uses at the most
-unsigned stage_blocks(long total)
-{
-    long blocks = (total + 255) / 256;
-    if (blocks > 1024) blocks = 1024;
-    return (unsigned)(blocks < 1 ? 1 : blocks);
+    amt_pass_set_layout(d, jobs);
 }
 
 template <typename T>
@@ -348,9 +309,9 @@ int stage_prep_launch(const amt_domain &d, int members, const StagePrepArrays &a
     stage_box<T>(d, jobs);
     constexpr long per = 16 / (long)sizeof(T);
     const long most = (long)jobs.nk * jobs.nj * ((jobs.ni + per - 1) / per);               // job ww, the larger of the two
-    hipLaunchKernelGGL(amt_stage_prep3_kernel<T>, dim3(stage_blocks(most), 2, (unsigned)members), dim3(256), 0, d.stream, jobs);
+    hipLaunchKernelGGL(amt_stage_prep3_kernel<T>, dim3(amt_pass_blocks(most), 2, (unsigned)members), dim3(256), 0, d.stream, jobs);
     AMT_HIP(hipGetLastError());
-    hipLaunchKernelGGL(amt_stage_prep2_kernel<T>, dim3(stage_blocks((long)jobs.ni * jobs.nj), 1, (unsigned)members), dim3(256), 0, d.stream, jobs);
+    hipLaunchKernelGGL(amt_stage_prep2_kernel<T>, dim3(amt_pass_blocks((long)jobs.ni * jobs.nj), 1, (unsigned)members), dim3(256), 0, d.stream, jobs);
     AMT_HIP(hipGetLastError());
     return AMT_OK;
 }
@@ -370,47 +331,24 @@ int stage_finish_launch(const amt_domain &d, int members, const StageFinishArray
     stage_box<T>(d, jobs);
     constexpr long per = 16 / (long)sizeof(T);
     const long most = (long)jobs.nk * jobs.nj * ((jobs.ni + per - 1) / per);
-    hipLaunchKernelGGL(amt_stage_finish_kernel<T>, dim3(stage_blocks(most), 3, (unsigned)members), dim3(256), 0, d.stream, jobs);
+    hipLaunchKernelGGL(amt_stage_finish_kernel<T>, dim3(amt_pass_blocks(most), 3, (unsigned)members), dim3(256), 0, d.stream, jobs);
     AMT_HIP(hipGetLastError());
     return AMT_OK;
 }
 
-// with_device_check: the pointer-level calls, which may be the first HIP call of a process, report a missing device
-// themselves -- behind the argument errors, which need none
-int stage_device_present()
-{
-    int ndev = 0;
-    AMT_HIP(hipGetDeviceCount(&ndev));
-    if (ndev < 1) return amt_fail(AMT_ERR_NO_DEVICE, "no HIP device visible");
-    return AMT_OK;
-}
-
-// the pointer-level calls run on the caller's current device
-int stage_current_device()
-{
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    return dev;
-}
-
-int stage_prep_run(const char *who, const amt_domain &d, int members, const StagePrepArrays &a, int rk_step, bool with_device_check)
+// the checks, then the launch (amt_pass_run)
+int stage_prep_run(const char *who, const amt_domain &d, int members, const StagePrepArrays &a, int rk_step, bool pointer_level)
 {
     bool empty = false;
-    int rc = stage_prep_check(who, d, members, a, rk_step, &empty);
-    if (rc != AMT_OK || empty) return rc;
-    if (with_device_check && (rc = stage_device_present()) != AMT_OK) return rc;
-    DeviceScope scope(with_device_check ? stage_current_device() : d.device);          // a handle's launches go to its device
-    return d.dtype_bytes == 8 ? stage_prep_launch<double>(d, members, a, rk_step) : stage_prep_launch<float>(d, members, a, rk_step);
+    const int rc = stage_prep_check(who, d, members, a, rk_step, &empty);
+    return amt_pass_run(rc, empty, d, pointer_level, [&](auto t) { return stage_prep_launch<decltype(t)>(d, members, a, rk_step); });
 }
 
-int stage_finish_run(const char *who, const amt_domain &d, int members, const StageFinishArrays &a, double dts, int n, bool with_device_check)
+int stage_finish_run(const char *who, const amt_domain &d, int members, const StageFinishArrays &a, double dts, int n, bool pointer_level)
 {
     bool empty = false;
-    int rc = stage_finish_check(who, d, members, a, n, &empty);
-    if (rc != AMT_OK || empty) return rc;
-    if (with_device_check && (rc = stage_device_present()) != AMT_OK) return rc;
-    DeviceScope scope(with_device_check ? stage_current_device() : d.device);
-    return d.dtype_bytes == 8 ? stage_finish_launch<double>(d, members, a, dts, n) : stage_finish_launch<float>(d, members, a, dts, n);
+    const int rc = stage_finish_check(who, d, members, a, n, &empty);
+    return amt_pass_run(rc, empty, d, pointer_level, [&](auto t) { return stage_finish_launch<decltype(t)>(d, members, a, dts, n); });
 }
 
 StagePrepArrays stage_prep_of_domain(const amt_domain *d)
@@ -418,6 +356,13 @@ StagePrepArrays stage_prep_of_domain(const amt_domain *d)
     return StagePrepArrays{d->field[AMT_F_T], d->field[AMT_F_T_1], d->stage_arr[0], d->field[AMT_F_WW], d->field[AMT_F_WW_1],
                            d->field[AMT_F_MU], d->stage_arr[1], d->stage_arr[2], d->field[AMT_F_MUTS], d->field[AMT_F_MUDF],
                            d->field[AMT_F_MUT], d->stage_arr[3]};
+}
+
+// the four arrays in the handle: t_old one 3-D field's extents, mu_old, mu_save and mub one 2-D field's, times the members
+AmtPassSetting stage_setting(amt_domain *d, int members)
+{
+    const size_t b3 = d->count(AMT_F_T) * (size_t)members * (size_t)d->dtype_bytes, b2 = d->count(AMT_F_MU) * (size_t)members * (size_t)d->dtype_bytes;
+    return AmtPassSetting{d->stage_arr, &d->stage_owned, 4, {b3, b2, b2, b2}, "four arrays", "an array", "the stage bracket", "an array"};
 }
 }  // namespace
 
@@ -438,12 +383,8 @@ int amt_stage_finish_domain(const char *who, amt_domain *d, int members, int n_s
 
 void amt_stage_release(amt_domain *d)
 {
-    for (void *&q : d->stage_arr) {
-        if (q && d->stage_owned) (void)hipFree(q);
-        q = nullptr;
-    }
+    amt_pass_setting_release(stage_setting(d, 1));
     d->stage_on = false;
-    d->stage_owned = false;
 }
 
 // amt_*_set_stage.  A refusal changes nothing.
@@ -454,67 +395,37 @@ int amt_stage_set_domain(const char *who, amt_domain *d, int members, int on, vo
         amt_stage_release(d);
         return AMT_OK;
     }
-    void *arr[4] = {t_old, mu_old, mu_save, mub};
-    const int given = (t_old != nullptr) + (mu_old != nullptr) + (mu_save != nullptr) + (mub != nullptr);
-    if (given != 0 && given != 4)
-        return amt_fail(AMT_ERR_INVALID_ARG, "%s: give all four arrays or none (the library then allocates them)", who);
-    // the library's own arrays handed back (amt_*_stage_ptr): they stay the library's; some of them among the caller's would be
-    // freed under the caller
-    const bool same = given == 4 && d->stage_owned && memcmp(arr, d->stage_arr, sizeof arr) == 0;
-    if (same) return AMT_OK;
-    if (given == 4 && d->stage_owned)
-        for (void *mine : d->stage_arr)
-            for (void *theirs : arr)
-                if (mine == theirs) return amt_fail(AMT_ERR_INVALID_ARG, "%s: an array the library allocated, mixed with others", who);
-    if (given == 4) {
-        amt_domain probe = *d;                                     // the checks against the caller's arrays, nothing enqueued
-        memcpy(probe.stage_arr, arr, sizeof arr);
+    void *const arr[4] = {t_old, mu_old, mu_save, mub};
+    const AmtPassSetting s = stage_setting(d, members);
+    int given;
+    bool same;
+    int rc = amt_pass_setting_offer(who, s, arr, &given, &same);
+    if (rc) return rc;
+    if (same) return AMT_OK;                                       // the library's own arrays handed back (amt_*_stage_ptr): nothing changes
+    rc = amt_pass_setting_take(who, d, members, s, arr, given, same, [&](void *const *theirs) {
+        amt_domain probe = *d;
+        memcpy(probe.stage_arr, theirs, sizeof probe.stage_arr);
         bool empty = false;
-        const int rc = stage_prep_check(who, probe, members, stage_prep_of_domain(&probe), 1, &empty);
-        if (rc) return rc;
-    } else {
-        if (members > 65535) return amt_fail(AMT_ERR_PRECONDITION, "%s: %d members: one launch covers at most 65535", who, members);
-        if (d->kts != 1 || d->kte != d->kde || d->kme < d->kte || d->kms > d->kts || d->its < d->ims || d->ite > d->ime || d->jts < d->jms || d->jte > d->jme)
-            return amt_fail(AMT_ERR_PRECONDITION, "%s: the handle's tile does not admit the stage bracket (kts == 1, kte == kde, tile inside memory)", who);
-    }
-    DeviceScope scope(d->device);                                  // behind every refusal but a failed allocation
-    if (given == 0) {
-        for (int k = 0; k < 4; ++k) {
-            const size_t bytes = d->count(k == 0 ? AMT_F_T : AMT_F_MU) * (size_t)members * (size_t)d->dtype_bytes;
-            arr[k] = nullptr;
-            if (hipMalloc(&arr[k], bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                for (int m = 0; m < k; ++m) (void)hipFree(arr[m]);
-                return amt_fail(AMT_ERR_ALLOC, "%s: no room for an array of %zu bytes", who, bytes);
-            }
-        }
-    }
-    amt_stage_release(d);
-    memcpy(d->stage_arr, arr, sizeof arr);
-    d->stage_owned = given == 0;
+        return stage_prep_check(who, probe, members, stage_prep_of_domain(&probe), 1, &empty);
+    });
+    if (rc) return rc;
     d->stage_on = true;
     return AMT_OK;
 }
 
 // ---- pointer level -------------------------------------------------------------------------------------------------------
-#define AMT_STAGE_BOUNDS_SIG                                                                                    \
-    int ids, int ide, int jds, int jde, int kde, int ims, int ime, int jms, int jme, int kms, int kme,          \
-    int its, int ite, int jts, int jte, int kts, int kte
-#define AMT_STAGE_DOMAIN(T)                                                                                     \
-    amt_domain d{(int)sizeof(T), 0, 0, 0, ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte}; \
-    d.stream = static_cast<hipStream_t>(hip_stream);
 #define AMT_STAGE_PREP_SIG(T)                                                                                   \
     void *hip_stream, int members, T *t, T *t_1, T *t_old, const T *ww, T *ww_1, T *mu, T *mu_old, T *mu_save,  \
-    T *muts, T *mudf, const T *mut, const T *mub, int rk_step, AMT_STAGE_BOUNDS_SIG
+    T *muts, T *mudf, const T *mut, const T *mub, int rk_step, AMT_BOUNDS_SIG
 #define AMT_STAGE_FINISH_SIG(T)                                                                                 \
     void *hip_stream, int members, T *t, const T *t_1, T *ww, const T *ww_1, T *mu, const T *mu_save,           \
-    const T *muts, const T *mut, T dts, int n_small_steps, const T *h_diabatic, AMT_STAGE_BOUNDS_SIG
+    const T *muts, const T *mut, T dts, int n_small_steps, const T *h_diabatic, AMT_BOUNDS_SIG
 #define AMT_STAGE_PREP_BODY(T, name)                                                                            \
-    AMT_STAGE_DOMAIN(T)                                                                                         \
-    return stage_prep_run(name, d, members, StagePrepArrays{t, t_1, t_old, ww, ww_1, mu, mu_old, mu_save, muts, mudf, mut, mub}, rk_step, true);
+    return stage_prep_run(name, amt_pass_domain((int)sizeof(T), hip_stream, AMT_BOUNDS_ARGS), members,          \
+                          StagePrepArrays{t, t_1, t_old, ww, ww_1, mu, mu_old, mu_save, muts, mudf, mut, mub}, rk_step, true);
 #define AMT_STAGE_FINISH_BODY(T, name)                                                                          \
-    AMT_STAGE_DOMAIN(T)                                                                                         \
-    return stage_finish_run(name, d, members, StageFinishArrays{t, t_1, ww, ww_1, mu, mu_save, muts, mut, h_diabatic}, (double)dts, n_small_steps, true);
+    return stage_finish_run(name, amt_pass_domain((int)sizeof(T), hip_stream, AMT_BOUNDS_ARGS), members,        \
+                            StageFinishArrays{t, t_1, ww, ww_1, mu, mu_save, muts, mut, h_diabatic}, (double)dts, n_small_steps, true);
 
 extern "C" int amt_stage_prep_device_f32(AMT_STAGE_PREP_SIG(float)) { AMT_STAGE_PREP_BODY(float, "amt_stage_prep_device_f32") }
 extern "C" int amt_stage_prep_device_f64(AMT_STAGE_PREP_SIG(double)) { AMT_STAGE_PREP_BODY(double, "amt_stage_prep_device_f64") }

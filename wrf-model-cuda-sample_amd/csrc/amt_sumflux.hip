@@ -127,46 +127,27 @@ struct SumfluxArrays {
     const void *u, *v, *ww, *u_1, *v_1, *ww_1, *muu, *muv, *msfuy, *msfvx_inv;
 };
 
-// Argument and precondition checks: host arithmetic only.  *empty: the tile box holds no cell (nothing to do).
+// a tile with one level holds cells of ww_m, one whose mass range is empty holds cells of ru_m or rv_m
+const AmtPassRules kSumfluxRules = {1, false, "two accumulators overlap", "an accumulator overlaps an input array"};
+
+// Argument and precondition checks (amt_pass.h): host arithmetic only.  *empty: the tile box holds no cell (nothing to do).
 int sumflux_check(const char *who, const amt_domain &s, int members, const SumfluxArrays &a, int iteration, int n, bool *empty)
 {
-    *empty = false;
-    if (!a.ru_m || !a.rv_m || !a.ww_m || !a.u || !a.v || !a.ww || !a.u_1 || !a.v_1 || !a.ww_1 || !a.muu || !a.muv || !a.msfuy || !a.msfvx_inv)
-        return amt_fail(AMT_ERR_INVALID_ARG, "%s: null array pointer", who);
-    if (members < 1) return amt_fail(AMT_ERR_INVALID_ARG, "%s: members = %d: an ensemble has at least one member", who, members);
+    // an accumulator may overlap no other array of the call (the inputs may alias one another)
+    const AmtPassArray arr[13] = {{a.ru_m, 3, true, false}, {a.rv_m, 3, true, false}, {a.ww_m, 3, true, false}, {a.u, 3, false, false},
+                                  {a.v, 3, false, false}, {a.ww, 3, false, false}, {a.u_1, 3, false, false}, {a.v_1, 3, false, false},
+                                  {a.ww_1, 3, false, false}, {a.muu, 2, false, false}, {a.muv, 2, false, false}, {a.msfuy, 2, false, false},
+                                  {a.msfvx_inv, 2, false, false}};
+    const int rc = amt_pass_check_arrays(who, members, arr, 13);
+    if (rc) return rc;
     if (n < 1) return amt_fail(AMT_ERR_INVALID_ARG, "%s: n_small_steps = %d: an acoustic loop has at least one sub-step", who, n);
     if (iteration < 1 || iteration > n) return amt_fail(AMT_ERR_INVALID_ARG, "%s: iteration %d is not in 1..%d", who, iteration, n);
-    if (s.ime < s.ims || s.jme < s.jms || s.kme < s.kms) return amt_fail(AMT_ERR_PRECONDITION, "%s: empty memory extents", who);
-    // an accumulator may overlap no other array of the call (the inputs may alias one another)
-    const size_t idim = s.ime - s.ims + 1, kdim = s.kme - s.kms + 1, jdim = s.jme - s.jms + 1;
-    const size_t b3 = idim * kdim * jdim * (size_t)members * (size_t)s.dtype_bytes, b2 = idim * jdim * (size_t)members * (size_t)s.dtype_bytes;
-    const void *acc[3] = {a.ru_m, a.rv_m, a.ww_m};
-    const void *in[10] = {a.u, a.v, a.ww, a.u_1, a.v_1, a.ww_1, a.muu, a.muv, a.msfuy, a.msfvx_inv};
-    auto overlap = [](const void *p, size_t pb, const void *r, size_t rb) {
-        const uintptr_t p0 = reinterpret_cast<uintptr_t>(p), r0 = reinterpret_cast<uintptr_t>(r);
-        return p0 < r0 + rb && r0 < p0 + pb;
-    };
-    for (int k = 0; k < 3; ++k) {
-        for (int m = k + 1; m < 3; ++m)
-            if (overlap(acc[k], b3, acc[m], b3)) return amt_fail(AMT_ERR_INVALID_ARG, "%s: two accumulators overlap", who);
-        for (int m = 0; m < 10; ++m)
-            if (overlap(acc[k], b3, in[m], m < 6 ? b3 : b2)) return amt_fail(AMT_ERR_INVALID_ARG, "%s: an accumulator overlaps an input array", who);
-    }
-    if (s.kts != 1) return amt_fail(AMT_ERR_PRECONDITION, "%s: kts = %d, the library needs kts == 1", who, s.kts);
-    if (s.kte != s.kde) return amt_fail(AMT_ERR_PRECONDITION, "%s: kte = %d is not kde = %d", who, s.kte, s.kde);
-    if (s.kme < s.kte || s.kms > s.kts) return amt_fail(AMT_ERR_PRECONDITION, "%s: levels kts:kte = %d:%d are not inside memory kms:kme = %d:%d", who, s.kts, s.kte, s.kms, s.kme);
-    if (s.ite < s.its || s.jte < s.jts || s.kte < s.kts) { *empty = true; return AMT_OK; }
-    if (s.its < s.ims || s.ite > s.ime || s.jts < s.jms || s.jte > s.jme)
-        return amt_fail(AMT_ERR_PRECONDITION, "%s: the tile %d:%d, %d:%d is not inside memory %d:%d, %d:%d", who,
-                        s.its, s.ite, s.jts, s.jte, s.ims, s.ime, s.jms, s.jme);
-    if (members > 65535) return amt_fail(AMT_ERR_PRECONDITION, "%s: %d members: one launch covers at most 65535", who, members);
-    return AMT_OK;
+    return amt_pass_check_box(who, s, members, arr, 13, kSumfluxRules, empty);
 }
 
 template <typename T>
 int sumflux_launch(const amt_domain &d, int members, const SumfluxArrays &a, int iteration, int n)
 {
-    const long idim = d.ime - d.ims + 1, kdim = d.kme - d.kms + 1, jdim = d.jme - d.jms + 1;
     AmtSumfluxJobs<T> jobs{};
     jobs.acc[0] = static_cast<T *>(a.ru_m); jobs.x[0] = static_cast<const T *>(a.u); jobs.x1[0] = static_cast<const T *>(a.u_1);
     jobs.acc[1] = static_cast<T *>(a.rv_m); jobs.x[1] = static_cast<const T *>(a.v); jobs.x1[1] = static_cast<const T *>(a.v_1);
@@ -174,38 +155,27 @@ int sumflux_launch(const amt_domain &d, int members, const SumfluxArrays &a, int
     jobs.fa[0] = static_cast<const T *>(a.muu); jobs.fb[0] = static_cast<const T *>(a.msfuy);
     jobs.fa[1] = static_cast<const T *>(a.muv); jobs.fb[1] = static_cast<const T *>(a.msfvx_inv);
     jobs.ni = d.ite - d.its + 1; jobs.nk = d.kte - d.kts + 1; jobs.nj = d.jte - d.jts + 1;
-    const int imass = (d.ite < d.ide - 1 ? d.ite : d.ide - 1) - d.its + 1;     // may be <= 0: no cell of the range
-    const int jmass = (d.jte < d.jde - 1 ? d.jte : d.jde - 1) - d.jts + 1;
+    int imass, jmass;                                              // may be <= 0: no cell of the range
+    amt_pass_mass_lengths(d, &imass, &jmass);
     jobs.ilen[0] = jobs.ni; jobs.klen[0] = jobs.nk - 1; jobs.jlen[0] = jmass;
     jobs.ilen[1] = imass;   jobs.klen[1] = jobs.nk - 1; jobs.jlen[1] = jobs.nj;
     jobs.ilen[2] = imass;   jobs.klen[2] = jobs.nk;     jobs.jlen[2] = jmass;
-    jobs.idim = idim; jobs.jstride3 = kdim * idim; jobs.mstride3 = idim * kdim * jdim; jobs.mstride2 = idim * jdim;
-    jobs.first3 = ((long)(d.jts - d.jms) * kdim + (d.kts - d.kms)) * idim + (d.its - d.ims);
-    jobs.first2 = (long)(d.jts - d.jms) * idim + (d.its - d.ims);
+    amt_pass_set_layout(d, jobs);
     jobs.n = (T)n;
     jobs.first = iteration == 1; jobs.last = iteration == n;
     constexpr long per = 16 / (long)sizeof(T);
     const long total = (long)jobs.nk * jobs.nj * ((jobs.ni + per - 1) / per);
-    long blocks = (total + 255) / 256;
-    if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(amt_sumflux_kernel<T>, dim3((unsigned)blocks, AMT_SUMFLUX_JOBS, (unsigned)members), dim3(256), 0, d.stream, jobs);
+    hipLaunchKernelGGL(amt_sumflux_kernel<T>, dim3(amt_pass_blocks(total), AMT_SUMFLUX_JOBS, (unsigned)members), dim3(256), 0, d.stream, jobs);
     AMT_HIP(hipGetLastError());
     return AMT_OK;
 }
 
-// the checks, then the launch.  with_device_check: the pointer-level calls, which may be the first HIP call of a process,
-// report a missing device themselves -- behind the argument errors, which need none
-int sumflux_run(const char *who, const amt_domain &d, int members, const SumfluxArrays &a, int iteration, int n, bool with_device_check)
+// the checks, then the launch (amt_pass_run)
+int sumflux_run(const char *who, const amt_domain &d, int members, const SumfluxArrays &a, int iteration, int n, bool pointer_level)
 {
     bool empty = false;
     const int rc = sumflux_check(who, d, members, a, iteration, n, &empty);
-    if (rc != AMT_OK || empty) return rc;
-    if (with_device_check) {
-        int ndev = 0;
-        AMT_HIP(hipGetDeviceCount(&ndev));
-        if (ndev < 1) return amt_fail(AMT_ERR_NO_DEVICE, "no HIP device visible");
-    }
-    return d.dtype_bytes == 8 ? sumflux_launch<double>(d, members, a, iteration, n) : sumflux_launch<float>(d, members, a, iteration, n);
+    return amt_pass_run(rc, empty, d, pointer_level, [&](auto t) { return sumflux_launch<decltype(t)>(d, members, a, iteration, n); });
 }
 
 SumfluxArrays sumflux_of_domain(const amt_domain *d)
@@ -213,6 +183,14 @@ SumfluxArrays sumflux_of_domain(const amt_domain *d)
     return SumfluxArrays{d->sumflux_acc[0], d->sumflux_acc[1], d->sumflux_acc[2], d->field[AMT_F_U], d->field[AMT_F_V], d->field[AMT_F_WW],
                          d->field[AMT_F_U_1], d->field[AMT_F_V_1], d->field[AMT_F_WW_1], d->field[AMT_F_MUU], d->field[AMT_F_MUV],
                          d->field[AMT_F_MSFUY], d->field[AMT_F_MSFVX_INV]};
+}
+
+// the three accumulators in the handle: one 3-D field's extents each, times the members
+AmtPassSetting sumflux_setting(amt_domain *d, int members)
+{
+    const size_t bytes = d->count(AMT_F_WW) * (size_t)members * (size_t)d->dtype_bytes;
+    return AmtPassSetting{d->sumflux_acc, &d->sumflux_owned, 3, {bytes, bytes, bytes}, "three accumulators", "an accumulator",
+                          "the flux averages", "three arrays"};
 }
 }  // namespace
 
@@ -228,13 +206,9 @@ int amt_sumflux_accumulate_domain(const char *who, amt_domain *d, int members)
 
 void amt_sumflux_release(amt_domain *d)
 {
-    for (void *&q : d->sumflux_acc) {
-        if (q && d->sumflux_owned) (void)hipFree(q);
-        q = nullptr;
-    }
+    amt_pass_setting_release(sumflux_setting(d, 1));
     d->sumflux_n = 0;
     d->sumflux_next = 1;
-    d->sumflux_owned = false;
 }
 
 // amt_*_set_sumflux.  A refusal changes nothing.
@@ -242,43 +216,20 @@ int amt_sumflux_set_domain(const char *who, amt_domain *d, int members, int n, v
 {
     if (n < 0) return amt_fail(AMT_ERR_INVALID_ARG, "%s: n_small_steps = %d", who, n);
     if (n == 0) { amt_sumflux_release(d); return AMT_OK; }
-    const int given = (ru_m != nullptr) + (rv_m != nullptr) + (ww_m != nullptr);
-    if (given != 0 && given != 3)
-        return amt_fail(AMT_ERR_INVALID_ARG, "%s: give all three accumulators or none (the library then allocates them)", who);
-    void *acc[3] = {ru_m, rv_m, ww_m};
-    const size_t bytes = d->count(AMT_F_WW) * (size_t)members * (size_t)d->dtype_bytes;
-    // the library's own arrays handed back (amt_*_sumflux_ptr): they stay the library's, n and the counter are set anew;
-    // one or two of them among the caller's would be freed under the caller
-    const bool same = given == 3 && d->sumflux_owned && memcmp(acc, d->sumflux_acc, sizeof acc) == 0;
-    if (given == 3 && d->sumflux_owned && !same)
-        for (void *mine : d->sumflux_acc)
-            for (void *theirs : acc)
-                if (mine == theirs) return amt_fail(AMT_ERR_INVALID_ARG, "%s: an accumulator the library allocated, mixed with others", who);
-    if (given == 3) {
-        amt_domain probe = *d;                                     // the checks against the caller's arrays, nothing enqueued
-        memcpy(probe.sumflux_acc, acc, sizeof acc);
+    void *const acc[3] = {ru_m, rv_m, ww_m};
+    const AmtPassSetting s = sumflux_setting(d, members);
+    int given;
+    bool same;                                                     // the library's own arrays handed back (amt_*_sumflux_ptr): they stay
+    int rc = amt_pass_setting_offer(who, s, acc, &given, &same);
+    if (rc) return rc;
+    rc = amt_pass_setting_take(who, d, members, s, acc, given, same, [&](void *const *arr) {
+        amt_domain probe = *d;
+        memcpy(probe.sumflux_acc, arr, sizeof probe.sumflux_acc);
         bool empty = false;
-        const int rc = sumflux_check(who, probe, members, sumflux_of_domain(&probe), 1, n, &empty);
-        if (rc) return rc;
-    } else {
-        if (members > 65535) return amt_fail(AMT_ERR_PRECONDITION, "%s: %d members: one launch covers at most 65535", who, members);
-        if (d->kts != 1 || d->kte != d->kde || d->kme < d->kte || d->kms > d->kts || d->its < d->ims || d->ite > d->ime || d->jts < d->jms || d->jte > d->jme)
-            return amt_fail(AMT_ERR_PRECONDITION, "%s: the handle's tile does not admit the flux averages (kts == 1, kte == kde, tile inside memory)", who);
-        for (int k = 0; k < 3; ++k) {
-            acc[k] = nullptr;
-            if (hipMalloc(&acc[k], bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                for (int m = 0; m < k; ++m) (void)hipFree(acc[m]);
-                return amt_fail(AMT_ERR_ALLOC, "%s: no room for three arrays of %zu bytes", who, bytes);
-            }
-        }
-    }
-    if (!same) {
-        amt_sumflux_release(d);
-        memcpy(d->sumflux_acc, acc, sizeof acc);
-        d->sumflux_owned = given == 0;
-    }
-    d->sumflux_n = n;
+        return sumflux_check(who, probe, members, sumflux_of_domain(&probe), 1, n, &empty);
+    });
+    if (rc) return rc;
+    d->sumflux_n = n;                                              // also for the library's own arrays: n and the counter are set anew
     d->sumflux_next = 1;
     return AMT_OK;
 }
@@ -286,13 +237,10 @@ int amt_sumflux_set_domain(const char *who, amt_domain *d, int members, int n, v
 #define AMT_SUMFLUX_SIG(T)                                                                                     \
     void *hip_stream, int members, T *ru_m, T *rv_m, T *ww_m, const T *u, const T *v, const T *ww,             \
     const T *u_1, const T *v_1, const T *ww_1, const T *muu, const T *muv, const T *msfuy, const T *msfvx_inv, \
-    int iteration, int n_small_steps, int ids, int ide, int jds, int jde, int kde,                             \
-    int ims, int ime, int jms, int jme, int kms, int kme, int its, int ite, int jts, int jte, int kts, int kte
+    int iteration, int n_small_steps, AMT_BOUNDS_SIG
 #define AMT_SUMFLUX_BODY(T, name)                                                                              \
-    amt_domain d{(int)sizeof(T), 0, 0, 0, ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte}; \
-    d.stream = static_cast<hipStream_t>(hip_stream);                                                           \
-    return sumflux_run(name, d, members, SumfluxArrays{ru_m, rv_m, ww_m, u, v, ww, u_1, v_1, ww_1, muu, muv, msfuy, msfvx_inv}, \
-                       iteration, n_small_steps, true);
+    return sumflux_run(name, amt_pass_domain((int)sizeof(T), hip_stream, AMT_BOUNDS_ARGS), members,            \
+                       SumfluxArrays{ru_m, rv_m, ww_m, u, v, ww, u_1, v_1, ww_1, muu, muv, msfuy, msfvx_inv}, iteration, n_small_steps, true);
 
 extern "C" int amt_sumflux_device_f32(AMT_SUMFLUX_SIG(float)) { AMT_SUMFLUX_BODY(float, "amt_sumflux_device_f32") }
 extern "C" int amt_sumflux_device_f64(AMT_SUMFLUX_SIG(double)) { AMT_SUMFLUX_BODY(double, "amt_sumflux_device_f64") }
