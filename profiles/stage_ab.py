@@ -16,7 +16,10 @@ read and three stores at rk_step 1, t and t_old read and two stores after that; 
 with h_diabatic (t, t_1 [, h_diabatic] read, t stored; ww, ww_1 read, ww stored).  A sweep moves 11.  Device time between two
 events on the handle's stream, the arms alternating, median of `reps`.
 
-  python profiles/stage_ab.py [--reps 7] [--cases 1x4096x60x4096,32x128x60x128] [--out FILE]
+  python profiles/stage_ab.py [--reps 7] [--cases 1x4096x60x4096,32x128x60x128] [--unaligned] [--out FILE]
+
+--unaligned lays the domain out with domain_bounds(..., aligned=False): rows that start off a 16-byte boundary, so that the
+chunks of the pass move element by element.
 """
 from __future__ import annotations
 
@@ -37,11 +40,11 @@ SWEEP_ELEMENTS = 11                       # what one sweep moves per cell at 60 
 SUBSTEPS = (1, 2, 4)                      # sub-steps of the three stages of a time step, for the bracket's share of it
 
 
-def measure(pkg, torch, members, dims, reps, seed=11):
+def measure(pkg, torch, members, dims, reps, aligned=True, seed=11):
     from wrf_model_cuda_sample_amd import lib
     S, L = pkg.synth, pkg.load_library()
     ni, nk, nj = dims
-    b = S.domain_bounds(ni, nk, nj, aligned=True)
+    b = S.domain_bounds(ni, nk, nj, aligned=aligned)
     cfg = pkg.GridConfig()
     ensemble = members > 1
     h = pkg.Ensemble(b, members, cfg, np.float64) if ensemble else S.NativeDomain(b, cfg, 8)
@@ -102,7 +105,7 @@ def measure(pkg, torch, members, dims, reps, seed=11):
         h.sync()
     finally:
         h.close() if ensemble else None
-    rec = {"case": f"stage {members}x{ni}x{nk}x{nj} f64", "members": members, "cells": cells}
+    rec = {"case": f"stage {members}x{ni}x{nk}x{nj} f64" + ("" if aligned else " unaligned"), "members": members, "cells": cells}
     for key, times in ms.items():
         rec[key] = {"ms": round(statistics.median(times), 4), "repeats": [round(x, 4) for x in times]}
     for which, k in ELEMENTS.items():
@@ -123,6 +126,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--cases", default="1x4096x60x4096,32x128x60x128")
+    ap.add_argument("--unaligned", action="store_true", help="rows off the 16-byte boundaries: the element-by-element chunks")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     import torch
@@ -132,7 +136,7 @@ def main():
     lines = []
     for case in args.cases.split(","):
         m, *dims = (int(x) for x in case.split("x"))
-        rec = measure(pkg, torch, m, tuple(dims), args.reps)
+        rec = measure(pkg, torch, m, tuple(dims), args.reps, aligned=not args.unaligned)
         lines.append(rec)
         print(json.dumps(rec), flush=True)
         if args.out:

@@ -43,3 +43,19 @@ def test_narrow_and_wide_paths_agree_and_the_wide_path_is_exact_past_2_to_the_32
     counts = [int(x) for x in r.stdout.replace(",", " ").split() if x.isdigit()]
     checks, narrow, wide, boundaries = counts[:4]
     assert narrow > 10000 and wide > 10000 and boundaries >= 100, r.stdout
+
+
+def test_chunk_load_and_store_move_exactly_cnt_elements_on_the_host(tmp_path):
+    """csrc/amt_chunk_io.h, the load and store the streaming kernels share, in a stand-alone program (tests/chunk_io_check.cpp):
+    both element types, every cnt in 0..kPer and every phase of the start, wide only for a whole chunk on a 16-byte boundary,
+    in guarded buffers and in allocations that end with the chunk.  ROCm's clang++: ext_vector_type rules out g++."""
+    from test_prho_host import _compiler
+    exe = tmp_path / "chunk_io_check"
+    r = subprocess.run([str(_compiler()), "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined",
+                        "-fno-sanitize-recover=undefined", "-I", str(ROOT / "wrf-model-cuda-sample_amd" / "csrc"),
+                        str(ROOT / "tests" / "chunk_io_check.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    # float: 5 counts x 4 phases, double: 3 x 2, each in two buffers, and the whole aligned chunk once more as a wide access
+    assert "chunk io: 56 loads, 56 stores, 4 of the cases wide, 0 failures" in r.stdout, r.stdout

@@ -5,27 +5,15 @@ needed."""
 import re
 from pathlib import Path
 
+from resource_remarks import _kernels
+
 ROOT = Path(__file__).resolve().parent.parent
 REMARKS = ROOT / "wrf-model-cuda-sample_amd" / "csrc" / "build" / "p_rho_resources.txt"
 
 
-def _kernels():
-    """mangled kernel name -> {remark label: integer value}"""
-    out, cur = {}, None
-    for line in REMARKS.read_text().splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+) \[-Rpass-analysis", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
-    return out
-
-
 def test_the_p_rho_kernels_have_no_scratch_no_spills_and_no_lds(pkg):
     assert REMARKS.exists(), "the build writes csrc/build/p_rho_resources.txt"
-    kernels = {k: v for k, v in _kernels().items() if "amt_p_rho_kernel" in k}
+    kernels = {k: v for k, v in _kernels(REMARKS).items() if "amt_p_rho_kernel" in k}
     # amt_p_rho_kernel<T, MODE>: I<f|d>Li<1|2>E in the mangled name
     assert sorted(re.search(r"amt_p_rho_kernelI([fd])Li([12])E", k).groups() for k in kernels) == [("d", "1"), ("d", "2"), ("f", "1"), ("f", "2")]
     for name, r in kernels.items():

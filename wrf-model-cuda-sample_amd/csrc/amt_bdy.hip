@@ -9,6 +9,7 @@
 // and ONE launch does the three fields of every strip, times the members of an ensemble.  Product, then sum: two roundings
 // (the library is built with -ffp-contract=off).
 #include "amt_internal.h"
+#include "amt_chunk_io.h"
 
 namespace {
 enum { AMT_BDY_MAX_JOBS = 12 };             // 4 strips x 3 fields
@@ -29,20 +30,16 @@ struct AmtBdyJobs {
     T dts;
 };
 
-template <typename T> struct AmtBdyVec;
-template <> struct AmtBdyVec<float> { typedef float type __attribute__((ext_vector_type(4))); };
-template <> struct AmtBdyVec<double> { typedef double type __attribute__((ext_vector_type(2))); };
-
 // Grid (blocks, jobs, members).  A work item is one 16-byte chunk of a run (its last chunk may be short), lanes run along
 // (chunk, level, row): along i for a row strip -- all three streams coalesced --, along (level, row) for a column, which touches
 // one line per element.  A whole chunk is ONE 16-byte load of each operand and one 16-byte store where dst AND tend lie on a
 // 16-byte boundary (decided per chunk from its two addresses, behind the member offset); a run's short last chunk and every
-// other chunk go element by element.
+// other chunk go element by element, into and out of the same vector (amt_chunk_io.h).
 // Nothing outside a run is read or written.  Offsets are 64-bit.  256 threads, no LDS.
 template <typename T>
 __global__ __launch_bounds__(256) void amt_bdy_kernel(AmtBdyJobs<T> jobs)
 {
-    typedef typename AmtBdyVec<T>::type V;
+    typedef typename AmtVec16<T>::type V;
     constexpr int kPer = 16 / (int)sizeof(T);
     const int q = blockIdx.y;
     const long moff = (long)blockIdx.z * jobs.member_stride[q];
@@ -60,21 +57,15 @@ __global__ __launch_bounds__(256) void amt_bdy_kernel(AmtBdyJobs<T> jobs)
         T *d = dst + at;
         const T *s = tend + at;
         const long left = len - first;
-        if (left >= kPer && ((reinterpret_cast<uintptr_t>(d) | reinterpret_cast<uintptr_t>(s)) & 15) == 0) {
-            const V old = *reinterpret_cast<const V *>(d), tn = *reinterpret_cast<const V *>(s);
-            V out;
-            for (int i = 0; i < kPer; ++i) {
-                const T step = dts * tn[i];
-                out[i] = old[i] + step;
-            }
-            *reinterpret_cast<V *>(d) = out;
-        } else {
-            const int n = left < kPer ? (int)left : kPer;
-            for (int i = 0; i < n; ++i) {
-                const T step = dts * s[i];
-                d[i] = d[i] + step;
-            }
+        const int cnt = left < kPer ? (int)left : kPer;
+        const bool wide = cnt == kPer && ((reinterpret_cast<uintptr_t>(d) | reinterpret_cast<uintptr_t>(s)) & 15) == 0;
+        const V old = amt_chunk_load<T>(d, wide, cnt), tn = amt_chunk_load<T>(s, wide, cnt);
+        V out;
+        for (int i = 0; i < kPer; ++i) {
+            const T step = dts * tn[i];
+            out[i] = old[i] + step;
         }
+        amt_chunk_store<T>(d, wide, cnt, out);
     }
 }
 

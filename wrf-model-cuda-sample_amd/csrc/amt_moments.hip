@@ -16,6 +16,7 @@
 // last chunk and every chunk off a 16-byte boundary move element by element.  Nothing outside the box is read or written.
 // The variance needs mean_d first: the members are read a second time, lines this thread loaded a moment before.
 #include "amt_internal.h"
+#include "amt_chunk_io.h"
 #include <limits.h>
 #include <math.h>
 
@@ -34,40 +35,11 @@ struct AmtMomentsArgs {
     int members;
 };
 
-template <typename T> struct AmtMomentsVec;
-template <> struct AmtMomentsVec<float> { typedef float type __attribute__((ext_vector_type(4))); };
-template <> struct AmtMomentsVec<double> { typedef double type __attribute__((ext_vector_type(2))); };
-
-// n elements of a chunk (n = kPer: a whole chunk); the elements past n are 0 and never stored
-template <typename T, typename V>
-__device__ inline V moments_load(const T *s, int n)
-{
-    constexpr int kPer = 16 / (int)sizeof(T);
-    if (n == kPer && (reinterpret_cast<uintptr_t>(s) & 15) == 0) return *reinterpret_cast<const V *>(s);
-    V x;
-#pragma unroll
-    for (int q = 0; q < kPer; ++q) x[q] = q < n ? s[q] : (T)0;
-    return x;
-}
-
-template <typename T, typename V>
-__device__ inline void moments_store(T *d, V x, int n)
-{
-    constexpr int kPer = 16 / (int)sizeof(T);
-    if (n == kPer && (reinterpret_cast<uintptr_t>(d) & 15) == 0) {
-        *reinterpret_cast<V *>(d) = x;
-        return;
-    }
-#pragma unroll
-    for (int q = 0; q < kPer; ++q)
-        if (q < n) d[q] = x[q];
-}
-
 // 256 threads, no LDS.  Offsets are 64-bit: a stacked fp32 array can pass 2^32 elements.
 template <typename T>
 __global__ __launch_bounds__(kMomentsThreads) void amt_moments_kernel(AmtMomentsArgs<T> p)
 {
-    typedef typename AmtMomentsVec<T>::type V;
+    typedef typename AmtVec16<T>::type V;
     constexpr int kPer = 16 / (int)sizeof(T);
     constexpr int kAhead = AMT_MOMENTS_AHEAD;
     const AmtBox &bx = p.box;
@@ -92,12 +64,16 @@ __global__ __launch_bounds__(kMomentsThreads) void amt_moments_kernel(AmtMoments
         const long at = bx.first + (long)jj * bx.jstride + (long)kk * bx.idim + e0;
         const int n = bx.ni - e0 < kPer ? bx.ni - e0 : kPer;
         const T *src = p.a + at;
+        // a chunk of n elements moves as one 16-byte access where it is whole and ITS address lies on a 16-byte boundary
+        // (amt_chunk_io.h: the lanes past n are 0 and never stored)
+        auto wide = [&](const T *q) { return n == kPer && (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+        auto member = [&](int m) { return src + (long)m * mstride; };
 
         double s[kPer];
         T lo[kPer], hi[kPer];
         bool bad[kPer];
         {
-            const V x = moments_load<T, V>(src, n);
+            const V x = amt_chunk_load<T>(src, wide(src), n);
 #pragma unroll
             for (int q = 0; q < kPer; ++q) {
                 s[q] = (double)x[q];
@@ -122,11 +98,11 @@ __global__ __launch_bounds__(kMomentsThreads) void amt_moments_kernel(AmtMoments
         for (; m + kAhead <= M; m += kAhead) {
             V x[kAhead];
 #pragma unroll
-            for (int u = 0; u < kAhead; ++u) x[u] = moments_load<T, V>(src + (long)(m + u) * mstride, n);
+            for (int u = 0; u < kAhead; ++u) x[u] = amt_chunk_load<T>(member(m + u), wide(member(m + u)), n);
 #pragma unroll
             for (int u = 0; u < kAhead; ++u) take(x[u]);
         }
-        for (; m < M; ++m) take(moments_load<T, V>(src + (long)m * mstride, n));
+        for (; m < M; ++m) take(amt_chunk_load<T>(member(m), wide(member(m)), n));
 
         double mean_d[kPer];
         V out;
@@ -135,7 +111,7 @@ __global__ __launch_bounds__(kMomentsThreads) void amt_moments_kernel(AmtMoments
             mean_d[q] = s[q] / dm;
             out[q] = (T)mean_d[q];
         }
-        if (p.mean) moments_store<T, V>(p.mean + at, out, n);
+        if (p.mean) amt_chunk_store<T>(p.mean + at, wide(p.mean + at), n, out);
 
         if (want_var) {
             double sq[kPer];
@@ -153,26 +129,26 @@ __global__ __launch_bounds__(kMomentsThreads) void amt_moments_kernel(AmtMoments
             for (; m + kAhead <= M; m += kAhead) {
                 V x[kAhead];
 #pragma unroll
-                for (int u = 0; u < kAhead; ++u) x[u] = moments_load<T, V>(src + (long)(m + u) * mstride, n);
+                for (int u = 0; u < kAhead; ++u) x[u] = amt_chunk_load<T>(member(m + u), wide(member(m + u)), n);
 #pragma unroll
                 for (int u = 0; u < kAhead; ++u) spread(x[u]);
             }
-            for (; m < M; ++m) spread(moments_load<T, V>(src + (long)m * mstride, n));
+            for (; m < M; ++m) spread(amt_chunk_load<T>(member(m), wide(member(m)), n));
 #pragma unroll
             for (int q = 0; q < kPer; ++q) out[q] = (T)(sq[q] / dm1);
-            moments_store<T, V>(p.var + at, out, n);
+            amt_chunk_store<T>(p.var + at, wide(p.var + at), n, out);
         }
         if (want_env) {
             const T qnan = (T)__builtin_nan("");
             if (p.lo) {
 #pragma unroll
                 for (int q = 0; q < kPer; ++q) out[q] = bad[q] ? qnan : lo[q];
-                moments_store<T, V>(p.lo + at, out, n);
+                amt_chunk_store<T>(p.lo + at, wide(p.lo + at), n, out);
             }
             if (p.hi) {
 #pragma unroll
                 for (int q = 0; q < kPer; ++q) out[q] = bad[q] ? qnan : hi[q];
-                moments_store<T, V>(p.hi + at, out, n);
+                amt_chunk_store<T>(p.hi + at, wide(p.hi + at), n, out);
             }
         }
     }

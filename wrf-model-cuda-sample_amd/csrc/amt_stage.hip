@@ -14,7 +14,7 @@
 // launches in stream order, the 3-D pass first (it never reads the stored muts), and finish, which has no such dependency, is
 // ONE.  Separate streaming passes around the acoustic loop: the march kernel is not touched.
 #include "amt_internal.h"
-#include "amt_chunk_index.h"
+#include "amt_chunk_io.h"
 
 namespace {
 // A job works on a box of nk * nj runs of `ni` contiguous elements, run r = (k, j) = (r % nk, r / nk) of member m starting at
@@ -31,10 +31,6 @@ struct AmtStageJobs {
     T c;                                                           // finish: dts * T(n_small_steps), rounded once in T
     int first, with_h;                                             // rk_step == 1; h_diabatic given
 };
-
-template <typename T> struct AmtStageVec;
-template <> struct AmtStageVec<float> { typedef float type __attribute__((ext_vector_type(4))); };
-template <> struct AmtStageVec<double> { typedef double type __attribute__((ext_vector_type(2))); };
 
 // Work item e of a 3-D job: one 16-byte chunk of a run, counted from the run's first element (the run's last chunk may be
 // short); lanes run along (chunk, k, j), along i first, so that every stream of a wave is coalesced.  Offsets are 64-bit.
@@ -87,12 +83,13 @@ __device__ __forceinline__ T amt_stage_finish_t(bool with_h, T x, T c, T mut, T 
 
 // The 3-D pass of prep.  Grid (blocks, 2 jobs, members): job 0 is t (reads mu or mu_old, mub, mut; never muts), job 1 the copy
 // ww_1 = ww.  A whole chunk moves as ONE 16-byte access per 3-D stream where all the 3-D addresses it touches lie on a 16-byte
-// boundary (decided per chunk from the streams' common phase behind the member offset); a run's short last chunk and every other chunk go element by
-// element, with the same arithmetic.  The 2-D operands are loaded element by element.  256 threads, no LDS.
+// boundary (decided per chunk from the streams' common phase behind the member offset); a run's short last chunk and every other
+// chunk go element by element.  Either way the chunk lives in the lanes of one vector (amt_chunk_io.h) and the arithmetic is
+// stated once.  The 2-D operands are loaded element by element, for the chunk's own elements only.  256 threads, no LDS.
 template <typename T>
 __global__ __launch_bounds__(256) void amt_stage_prep3_kernel(AmtStageJobs<T> jobs)
 {
-    typedef typename AmtStageVec<T>::type V;
+    typedef typename AmtVec16<T>::type V;
     constexpr int kPer = 16 / (int)sizeof(T);
     const int q = blockIdx.y;
     const long moff3 = (long)blockIdx.z * jobs.mstride3 + jobs.first3, moff2 = (long)blockIdx.z * jobs.mstride2 + jobs.first2;
@@ -109,11 +106,8 @@ __global__ __launch_bounds__(256) void amt_stage_prep3_kernel(AmtStageJobs<T> jo
             long at3, at2;
             int cnt;
             amt_stage_chunk<kPer>(e, chunks, nk, ni, narrow, jobs.idim, jobs.jstride3, at3, at2, cnt);
-            if (cnt == kPer && amt_stage_aligned<T>(phase, at3)) {
-                *reinterpret_cast<V *>(ww_1 + at3) = *reinterpret_cast<const V *>(ww + at3);
-            } else {
-                for (int i = 0; i < cnt; ++i) ww_1[at3 + i] = ww[at3 + i];
-            }
+            const bool wide = cnt == kPer && amt_stage_aligned<T>(phase, at3);
+            amt_chunk_store<T>(ww_1 + at3, wide, cnt, amt_chunk_load<T>(ww + at3, wide, cnt));
         }
         return;
     }
@@ -124,28 +118,20 @@ __global__ __launch_bounds__(256) void amt_stage_prep3_kernel(AmtStageJobs<T> jo
         long at3, at2;
         int cnt;
         amt_stage_chunk<kPer>(e, chunks, nk, ni, narrow, jobs.idim, jobs.jstride3, at3, at2, cnt);
-        if (cnt == kPer && amt_stage_aligned<T>(phase, at3)) {
-            const V x = *reinterpret_cast<const V *>(t + at3);
-            V old = x, out;
-            if (!first) old = *reinterpret_cast<const V *>(t_old + at3);
-            for (int i = 0; i < kPer; ++i) {
-                const T s = mub[at2 + i] + m2[at2 + i];
-                out[i] = amt_stage_prep_t<T>(s, old[i], mut[at2 + i], x[i]);
-            }
-            if (first) *reinterpret_cast<V *>(t_old + at3) = x;
-            *reinterpret_cast<V *>(t_1 + at3) = x;
-            *reinterpret_cast<V *>(t + at3) = out;
-        } else {
-            for (int i = 0; i < cnt; ++i) {
-                const T x = t[at3 + i];
-                const T old = first ? x : t_old[at3 + i];
-                const T s = mub[at2 + i] + m2[at2 + i];
-                const T out = amt_stage_prep_t<T>(s, old, mut[at2 + i], x);
-                if (first) t_old[at3 + i] = x;
-                t_1[at3 + i] = x;
-                t[at3 + i] = out;
-            }
+        const bool wide = cnt == kPer && amt_stage_aligned<T>(phase, at3);
+        // every load of the chunk is issued before the first use of one
+        V old = T(0), out;
+        if (!first) old = amt_chunk_load<T>(t_old + at3, wide, cnt);
+        const V x = amt_chunk_load<T>(t + at3, wide, cnt);
+        const V b = amt_chunk_load<T>(mub + at2, false, cnt), m = amt_chunk_load<T>(m2 + at2, false, cnt);
+        const V mt = amt_chunk_load<T>(mut + at2, false, cnt);
+        for (int i = 0; i < kPer; ++i) {
+            const T s = b[i] + m[i];
+            out[i] = amt_stage_prep_t<T>(s, first ? x[i] : old[i], mt[i], x[i]);
         }
+        if (first) amt_chunk_store<T>(t_old + at3, wide, cnt, x);
+        amt_chunk_store<T>(t_1 + at3, wide, cnt, x);
+        amt_chunk_store<T>(t + at3, wide, cnt, out);
     }
 }
 
@@ -180,7 +166,7 @@ __global__ __launch_bounds__(256) void amt_stage_prep2_kernel(AmtStageJobs<T> jo
 template <typename T>
 __global__ __launch_bounds__(256) void amt_stage_finish_kernel(AmtStageJobs<T> jobs)
 {
-    typedef typename AmtStageVec<T>::type V;
+    typedef typename AmtVec16<T>::type V;
     constexpr int kPer = 16 / (int)sizeof(T);
     const int q = blockIdx.y;
     const long moff3 = (long)blockIdx.z * jobs.mstride3 + jobs.first3, moff2 = (long)blockIdx.z * jobs.mstride2 + jobs.first2;
@@ -208,14 +194,11 @@ __global__ __launch_bounds__(256) void amt_stage_finish_kernel(AmtStageJobs<T> j
             long at3, at2;
             int cnt;
             amt_stage_chunk<kPer>(e, chunks, nk, ni, narrow, jobs.idim, jobs.jstride3, at3, at2, cnt);
-            if (cnt == kPer && amt_stage_aligned<T>(phase, at3)) {
-                V a = *reinterpret_cast<const V *>(ww + at3);
-                const V b = *reinterpret_cast<const V *>(ww_1 + at3);
-                for (int i = 0; i < kPer; ++i) a[i] = a[i] + b[i];
-                *reinterpret_cast<V *>(ww + at3) = a;
-            } else {
-                for (int i = 0; i < cnt; ++i) ww[at3 + i] = ww[at3 + i] + ww_1[at3 + i];
-            }
+            const bool wide = cnt == kPer && amt_stage_aligned<T>(phase, at3);
+            V a = amt_chunk_load<T>(ww + at3, wide, cnt);
+            const V b = amt_chunk_load<T>(ww_1 + at3, wide, cnt);
+            for (int i = 0; i < kPer; ++i) a[i] = a[i] + b[i];
+            amt_chunk_store<T>(ww + at3, wide, cnt, a);
         }
         return;
     }
@@ -227,17 +210,14 @@ __global__ __launch_bounds__(256) void amt_stage_finish_kernel(AmtStageJobs<T> j
         long at3, at2;
         int cnt;
         amt_stage_chunk<kPer>(e, chunks, nk, ni, narrow, jobs.idim, jobs.jstride3, at3, at2, cnt);
-        if (cnt == kPer && amt_stage_aligned<T>(phase, at3)) {
-            V x = *reinterpret_cast<const V *>(t + at3);
-            const V t1 = *reinterpret_cast<const V *>(t_1 + at3);
-            V hv = t1;
-            if (with_h) hv = *reinterpret_cast<const V *>(h + at3);
-            for (int i = 0; i < kPer; ++i) x[i] = amt_stage_finish_t<T>(with_h, x[i], c, mut[at2 + i], hv[i], t1[i], muts[at2 + i]);
-            *reinterpret_cast<V *>(t + at3) = x;
-        } else {
-            for (int i = 0; i < cnt; ++i)
-                t[at3 + i] = amt_stage_finish_t<T>(with_h, t[at3 + i], c, mut[at2 + i], with_h ? h[at3 + i] : T(0), t_1[at3 + i], muts[at2 + i]);
-        }
+        const bool wide = cnt == kPer && amt_stage_aligned<T>(phase, at3);
+        V hv = T(0);                                               // every load is issued before the first use of one
+        if (with_h) hv = amt_chunk_load<T>(h + at3, wide, cnt);
+        V x = amt_chunk_load<T>(t + at3, wide, cnt);
+        const V t1 = amt_chunk_load<T>(t_1 + at3, wide, cnt);
+        const V mt = amt_chunk_load<T>(mut + at2, false, cnt), ms = amt_chunk_load<T>(muts + at2, false, cnt);
+        for (int i = 0; i < kPer; ++i) x[i] = amt_stage_finish_t<T>(with_h, x[i], c, mt[i], hv[i], t1[i], ms[i]);
+        amt_chunk_store<T>(t + at3, wide, cnt, x);
     }
 }
 

@@ -8,7 +8,7 @@
 // one short of the domain's end); at iteration 1 the tile's cells outside it become +0.0.  ONE launch does the three
 // accumulators, times the members of an ensemble.  A separate streaming pass behind the sweep: the march kernel is not touched.
 #include "amt_internal.h"
-#include "amt_chunk_index.h"
+#include "amt_chunk_io.h"
 
 namespace {
 enum { AMT_SUMFLUX_JOBS = 3 };              // ru_m, rv_m, ww_m
@@ -29,10 +29,6 @@ struct AmtSumfluxJobs {
     int first, last;                                               // iteration == 1, iteration == n
 };
 
-template <typename T> struct AmtSumfluxVec;
-template <> struct AmtSumfluxVec<float> { typedef float type __attribute__((ext_vector_type(4))); };
-template <> struct AmtSumfluxVec<double> { typedef double type __attribute__((ext_vector_type(2))); };
-
 // what the last sub-step adds to the average: job 0 (muu * u_1) / msfuy, job 1 (muv * v_1) * msfvx_inv, job 2 ww_1
 template <typename T>
 __device__ __forceinline__ T amt_sumflux_base(int q, T x1, T fa, T fb)
@@ -43,16 +39,17 @@ __device__ __forceinline__ T amt_sumflux_base(int q, T x1, T fa, T fb)
 }
 
 // Grid (blocks, 3 jobs, members).  A work item is one 16-byte chunk of a run (its last chunk may be short), lanes run along
-// (chunk, k, j): along i first, so that every stream of a wave is coalesced.  A whole chunk inside the range moves as ONE
-// 16-byte access per 3-D stream where all of them lie on a 16-byte boundary (decided per chunk from its addresses, behind the
-// member offset); a run's short last chunk, a chunk that holds the cell past the range and every other chunk go element by
-// element.  The 2-D factors are loaded at the last iteration only.  A run outside the range in k or j, and the cell past it in
-// i, is zeroed at the first iteration and not touched otherwise.  The arithmetic is the same on both paths.
+// (chunk, k, j): along i first, so that every stream of a wave is coalesced.  `live` of a chunk's `cnt` elements lie inside
+// the accumulator's range: none in a run outside it in k or j, all but the cell past it in i otherwise.  Load, add, average and
+// store happen over `live`, once, on the lanes of a vector (amt_chunk_io.h); at the first iteration the tile's elements
+// live..cnt-1 become +0.0, otherwise they are not touched.  A chunk moves as ONE 16-byte access per 3-D stream where it is
+// whole, all or none of it is live and every address it touches lies on a 16-byte boundary (decided per chunk, behind the
+// member offset); every other chunk goes element by element.  The 2-D factors are loaded at the last iteration only.
 // Nothing outside the tile box is read or written.  Offsets are 64-bit.  256 threads, no LDS.
 template <typename T>
 __global__ __launch_bounds__(256) void amt_sumflux_kernel(AmtSumfluxJobs<T> jobs)
 {
-    typedef typename AmtSumfluxVec<T>::type V;
+    typedef typename AmtVec16<T>::type V;
     constexpr int kPer = 16 / (int)sizeof(T);
     const int q = blockIdx.y;
     const long moff3 = (long)blockIdx.z * jobs.mstride3 + jobs.first3, moff2 = (long)blockIdx.z * jobs.mstride2 + jobs.first2;
@@ -68,57 +65,40 @@ __global__ __launch_bounds__(256) void amt_sumflux_kernel(AmtSumfluxJobs<T> jobs
     const bool narrow = total <= 0x7fffffffL;                      // wave-uniform: 32-bit divisions where they suffice
     for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
         const AmtChunk c = amt_chunk_index<kPer>(e, chunks, nk, ni, narrow);
-        const long j = c.j, k = c.k, i0 = c.i0;                    // i0: first element of this chunk inside its run
-        const long at3 = j * jobs.jstride3 + k * jobs.idim + i0, at2 = j * jobs.idim + i0;
+        const long at3 = c.j * jobs.jstride3 + c.k * jobs.idim + c.i0, at2 = c.j * jobs.idim + c.i0;
         const int cnt = c.cnt;
+        const long in = c.k >= klen || c.j >= jlen ? 0 : ilen - c.i0;
+        const int live = in < 0 ? 0 : in < cnt ? (int)in : cnt;
+        if (live == 0 && !first) continue;                         // nothing of the range: only the first iteration zeroes it
         T *a = acc + at3;
-        if (k >= klen || j >= jlen) {                              // a run of the tile outside the accumulator's range
-            if (first) {
-                if (cnt == kPer && (reinterpret_cast<uintptr_t>(a) & 15) == 0) {
-                    V z;
-                    for (int i = 0; i < kPer; ++i) z[i] = T(0);
-                    *reinterpret_cast<V *>(a) = z;
-                } else {
-                    for (int i = 0; i < cnt; ++i) a[i] = T(0);
-                }
-            }
-            continue;
-        }
         const T *xs = x + at3, *x1s = x1 + at3;
-        uintptr_t bits = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(xs);
-        if (last) bits |= reinterpret_cast<uintptr_t>(x1s);
-        if (cnt == kPer && i0 + kPer <= ilen && (bits & 15) == 0) {
-            V s = *reinterpret_cast<const V *>(xs);
-            if (first) {
-                for (int i = 0; i < kPer; ++i) s[i] = T(0) + s[i];
-            } else {
-                const V old = *reinterpret_cast<const V *>(a);
-                for (int i = 0; i < kPer; ++i) s[i] = old[i] + s[i];
-            }
+        uintptr_t bits = reinterpret_cast<uintptr_t>(a);
+        if (live) bits |= reinterpret_cast<uintptr_t>(xs);
+        if (live && last) bits |= reinterpret_cast<uintptr_t>(x1s);
+        const bool wide = cnt == kPer && (live == kPer || live == 0) && (bits & 15) == 0;
+        V s = T(0);
+        if (live) {
+            // every load of the chunk is issued before the first use of one
+            V b = s, f0 = s, f1 = s;                               // not used unless loaded: job 2 has no factors
+            const V xv = amt_chunk_load<T>(xs, wide, live);
+            if (!first) s = amt_chunk_load<T>(a, wide, live);
             if (last) {
-                const V b = *reinterpret_cast<const V *>(x1s);
+                b = amt_chunk_load<T>(x1s, wide, live);
+                if (q != 2) {
+                    f0 = amt_chunk_load<T>(fa + at2, false, live);
+                    f1 = amt_chunk_load<T>(fb + at2, false, live);
+                }
+            }
+            for (int i = 0; i < kPer; ++i) s[i] = s[i] + xv[i];    // T(0) + x at the first iteration: -0.0 becomes +0.0
+            if (last)
                 for (int i = 0; i < kPer; ++i) {
-                    const T f0 = q == 2 ? T(0) : fa[at2 + i], f1 = q == 2 ? T(0) : fb[at2 + i];
                     const T avg = s[i] / n;
-                    s[i] = avg + amt_sumflux_base<T>(q, b[i], f0, f1);
+                    s[i] = avg + amt_sumflux_base<T>(q, b[i], f0[i], f1[i]);
                 }
-            }
-            *reinterpret_cast<V *>(a) = s;
-        } else {
-            for (int i = 0; i < cnt; ++i) {
-                if (i0 + i >= ilen) {                              // the tile's cell past the range in i
-                    if (first) a[i] = T(0);
-                    continue;
-                }
-                T s = first ? T(0) + xs[i] : a[i] + xs[i];
-                if (last) {
-                    const T f0 = q == 2 ? T(0) : fa[at2 + i], f1 = q == 2 ? T(0) : fb[at2 + i];
-                    const T avg = s / n;
-                    s = avg + amt_sumflux_base<T>(q, x1s[i], f0, f1);
-                }
-                a[i] = s;
-            }
         }
+        if (first)                                                 // the tile's cells outside the range
+            for (int i = 0; i < kPer; ++i) s[i] = i < live ? s[i] : T(0);
+        amt_chunk_store<T>(a, wide, first ? cnt : live, s);
     }
 }
 
