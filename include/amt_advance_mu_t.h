@@ -1141,6 +1141,108 @@ int amt_ensemble_set_p_rho(amt_ensemble *e, int mode, int per_sweep, double t0, 
 void *amt_ensemble_p_rho_ptr(amt_ensemble *e, int which);
 int amt_ensemble_p_rho(amt_ensemble *e, int step);
 
+/* ------------------------------------------------------------------------
+ * (17) The momentum update that opens an acoustic sub-step: advance_uv, on the device.  In solve_em
+ *      advance_uv precedes every advance_mu_t of the acoustic loop: from the p, al, ph that calc_p_rho (16) has left and the mu,
+ *      mudf of the last sweep it advances u and v by the horizontal pressure gradient and the divergence damping.  The
+ *      reference has no source for the routine: the definition below is this library's contract, modelled on WRF's routine,
+ *      without the hybrid coordinate (c1h, c2h), top_lid and open / symmetric boundaries.
+ *      Indices are Fortran-inclusive and global, on a tile its..ite, jts..jte with kts == 1 and kte == kde; T is the arrays'
+ *      type.  Every operation is rounded once in T, there is no fused multiply-add, divides are IEEE divides, expressions
+ *      associate exactly as written; for fp32 every scalar is rounded to float first; dx = T(1)/rdx, dy = T(1)/rdy.
+ *      Outputs, in place: u, v.  3-D inputs: ru_tend, rv_tend, p, pb, ph (w levels kts..kte), php, alt, al, cqu, cqv.  2-D
+ *      inputs: mu, muu, muv, mudf, msfux, msfuy, msfvx, msfvx_inv, msfvy.  1-D inputs over kms..kme, shared by the members:
+ *      fnm, fnp, rdnw.  `members` >= 1 patches are member-stacked as in (8).  The flags are amt_compute_window's.
+ *      RANGES, with clip = specified || nested:
+ *        columns, clip && !periodic_x:  i_start = max(its, ids+1), i_end = min(ite, ide-2), i_endu = min(ite, ide-1)
+ *        columns, otherwise:            i_start = its, i_endu = ite, i_end = min(ite, ide-1)
+ *        rows, clip:                    j_start = max(jts, jds+1), j_end = min(jte, jde-2), j_endv = min(jte, jde-1)
+ *        rows, otherwise:               j_start = jts, j_endv = jte, j_end = min(jte, jde-1)
+ *        levels:                        k = kts..kte-1
+ *      U PART, j = j_start..j_end, i = i_start..i_endu:
+ *        mr   = msfux(i,j) / msfuy(i,j)
+ *        c    = ((mr * T(0.5)) * rdx) * muu(i,j)
+ *        g    = (((ph(i,k+1,j) - ph(i-1,k+1,j)) + (ph(i,k,j) - ph(i-1,k,j)))
+ *                + ((alt(i,k,j) + alt(i-1,k,j)) * (p(i,k,j) - p(i-1,k,j))))
+ *                + ((al(i,k,j) + al(i-1,k,j)) * (pb(i,k,j) - pb(i-1,k,j)))
+ *        dpxy = c * g
+ *        non_hydrostatic only:
+ *          s(k)     = p(i,k,j) + p(i-1,k,j)
+ *          dpn(kts) = T(0.5) * (((cf1*s(1)) + (cf2*s(2))) + (cf3*s(3)))
+ *          dpn(k)   = T(0.5) * ((fnm(k)*s(k)) + (fnp(k)*s(k-1)))          k = kts+1..kte-1
+ *          dpn(kte) = T(0)
+ *          dpxy = dpxy + (((mr * rdx) * (php(i,k,j) - php(i-1,k,j)))
+ *                         * ((rdnw(k) * (dpn(k+1) - dpn(k))) - (T(0.5) * (mu(i-1,j) + mu(i,j)))))
+ *        mdx  = (((-emdiv) * dx) * (mudf(i,j) - mudf(i-1,j))) / msfuy(i,j)
+ *        u    = ((u + (dts * ru_tend)) - ((dts * cqu) * dpxy)) + mdx
+ *      V PART, j = j_start..j_endv, i = i_start..i_end: the same text with (i, j-1) for (i-1, j), mr = msfvy(i,j) / msfvx(i,j),
+ *        rdy for rdx, muv for muu, cqv for cqu, rv_tend for ru_tend and
+ *        mdy = (((-emdiv) * dy) * (mudf(i,j) - mudf(i,j-1))) * msfvx_inv(i,j)
+ *      Always bit-unchanged, NaN payloads included: every cell of u, v outside its range, every memory level outside
+ *      kts..kte-1, every input.  No input cell outside those the formulas name is read: php, mu, fnm, fnp, rdnw not at all
+ *      when non_hydrostatic == 0.  The cells named include the mass cells at i_start-1, at j_start-1 and at column ide / row
+ *      jde where i_endu / j_endv reach them: they must lie in memory and the caller supplies their values, as WRF's boundary
+ *      code and halo exchange do.  No atomics, no workspace.  Inputs may alias one another; u and v overlap no other array.
+ *      One launch.
+ *      Reported before any device call, with or without a device, the arrays untouched, in this order: AMT_ERR_INVALID_ARG: a
+ *      NULL array; members < 1.  AMT_ERR_PRECONDITION: empty memory extents.  AMT_ERR_INVALID_ARG: u or v overlaps another
+ *      array.  AMT_ERR_PRECONDITION: kts != 1; kte != kde; kme < kte; the tile outside memory; more than 65535 members;
+ *      non_hydrostatic with kde < 4; the cells read at i_start-1, j_start-1, i_endu, j_endv outside ims..ime, jms..jme.
+ *      Empty (AMT_OK, nothing enqueued): the empty tile, kte == kts, both parts without a cell.
+ *      NOT provided: the one-shot host-array calls of (1); advance_w; the stage bracket for u, v; the spec_bdyupdate
+ *      of u, v on the ring; top_lid; open / symmetric boundaries; the hybrid coordinate; any exchange between ranks.
+ * ------------------------------------------------------------------------ */
+/* pointer level; asynchronous on hip_stream (NULL = the default stream) */
+int amt_advance_uv_device_f32(
+    void *hip_stream, int members, int non_hydrostatic, float *u, float *v, const float *ru_tend, const float *rv_tend,
+    const float *p, const float *pb, const float *ph, const float *php, const float *alt, const float *al,
+    const float *mu, const float *muu, const float *muv, const float *mudf, const float *cqu, const float *cqv,
+    const float *msfux, const float *msfuy, const float *msfvx, const float *msfvx_inv, const float *msfvy,
+    const float *fnm, const float *fnp, const float *rdnw,
+    float rdx, float rdy, float dts, float cf1, float cf2, float cf3, float emdiv,
+    int periodic_x, int specified, int nested,
+    int ids, int ide, int jds, int jde, int kde,
+    int ims, int ime, int jms, int jme, int kms, int kme,
+    int its, int ite, int jts, int jte, int kts, int kte);
+int amt_advance_uv_device_f64(
+    void *hip_stream, int members, int non_hydrostatic, double *u, double *v, const double *ru_tend, const double *rv_tend,
+    const double *p, const double *pb, const double *ph, const double *php, const double *alt, const double *al,
+    const double *mu, const double *muu, const double *muv, const double *mudf, const double *cqu, const double *cqv,
+    const double *msfux, const double *msfuy, const double *msfvx, const double *msfvx_inv, const double *msfvy,
+    const double *fnm, const double *fnp, const double *rdnw,
+    double rdx, double rdy, double dts, double cf1, double cf2, double cf3, double emdiv,
+    int periodic_x, int specified, int nested,
+    int ids, int ide, int jds, int jde, int kde,
+    int ims, int ime, int jms, int jme, int kms, int kme,
+    int its, int ite, int jts, int jte, int kts, int kte);
+/* on = 0: off (the default) and what the library allocated is freed; the handle's destroy frees it too.  on != 0 with ru_tend,
+ * rv_tend, pb, php, cqu, cqv, msfux, msfvx, msfvy all NULL: the library allocates the nine arrays (the six 3-D ones of a 3-D
+ * field's extents, the three map factors of a 2-D field's, times the members of an ensemble; the host fills them through
+ * amt_domain_uv_ptr); all nine given: the caller's device arrays are used and never freed; a mix is AMT_ERR_INVALID_ARG.  (The
+ * library's own nine may be handed back: per_sweep and the scalars are set anew.)  The setting needs the pressure diagnosis
+ * (16) on: it reads that setting's al, p, ph, alt, and non_hydrostatic is mode 1; AMT_ERR_PRECONDITION otherwise, also from
+ * amt_domain_uv after amt_domain_set_p_rho(d, 0, ...).  u, v, mu, muu, muv, mudf, msfuy, msfvx_inv, fnm, fnp, rdnw are the
+ * handle's fields, rdx, rdy, dts its scalars.  A refusal changes nothing.
+ * per_sweep != 0: every sweep of amt_domain_step / amt_domain_step_timed is preceded by one update, in front of the cyclic
+ * refresh of (9).  amt_domain_tune_placement's timed sweeps are not preceded by it.  Under amt_slab_* and amt_grid_* the step
+ * calls (step, step_timed, step_begin, step_end) return AMT_ERR_PRECONDITION with a text before they enqueue anything: the
+ * halo exchange of p, al, ph, mu, mudf is not provided.
+ * A handle with cyclic axes (amt_domain_set_cyclic) refreshes, on the same stream in front of every update, the wrap cells of
+ * p, al, ph, alt, pb, php, mu, mudf: column ide <- ids and ids-1 <- ide-1 over the rows of the u part, row jde <- jds and
+ * jds-1 <- jde-1 over the columns of the v part, every memory level, elements moved as bits. */
+int amt_domain_set_uv(amt_domain *d, int on, int per_sweep, double emdiv, double cf1, double cf2, double cf3,
+                      void *ru_tend, void *rv_tend, void *pb, void *php, void *cqu, void *cqv,
+                      void *msfux, void *msfvx, void *msfvy);
+void *amt_domain_uv_ptr(amt_domain *d, int which);   /* 0 ru_tend, 1 rv_tend, 2 pb, 3 php, 4 cqu, 5 cqv, 6 msfux, 7 msfvx, 8 msfvy; NULL while off */
+/* one update now, asynchronous on the handle's stream (the caller's for a wrapped handle); AMT_ERR_PRECONDITION while off */
+int amt_domain_uv(amt_domain *d);
+/* the same for an ensemble: all members in one launch, member-stacked arrays */
+int amt_ensemble_set_uv(amt_ensemble *e, int on, int per_sweep, double emdiv, double cf1, double cf2, double cf3,
+                        void *ru_tend, void *rv_tend, void *pb, void *php, void *cqu, void *cqv,
+                        void *msfux, void *msfvx, void *msfvy);
+void *amt_ensemble_uv_ptr(amt_ensemble *e, int which);
+int amt_ensemble_uv(amt_ensemble *e);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,7 +27,7 @@ from .lib import FieldStats, FieldDiff, GuardReport, REGION_WINDOW, REGION_MEMOR
 from .api import advance_mu_t, bind_device_call, compute_window, VARIANT_AUTO, VARIANT_COLUMN, VARIANT_MARCH, LAUNCH_BESIDE_OTHERS  # noqa: F401
 from .api import host_cache_enable, host_invalidate, host_defer, host_fetch, host_stale, host_release, held_arrays  # noqa: F401
 from .api import host_set_devices, host_devices  # noqa: F401
-from .api import cyclic_fill, spec_bdy_update, sumflux, stage_prep, stage_finish, p_rho, CYCLIC_X, CYCLIC_Y  # noqa: F401
+from .api import cyclic_fill, spec_bdy_update, sumflux, stage_prep, stage_finish, p_rho, advance_uv, CYCLIC_X, CYCLIC_Y  # noqa: F401
 from . import synth  # noqa: F401
 from . import patch  # noqa: F401
 from . import wrfdump  # noqa: F401

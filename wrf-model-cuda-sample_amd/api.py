@@ -258,6 +258,27 @@ def p_rho(mode, step, al, p, ph, pm1, alt, c2a, t, t_old, mu, muts, rdnw, znu, d
                 (ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte))
 
 
+def advance_uv(non_hydrostatic, u, v, ru_tend, rv_tend, p, pb, ph, php, alt, al, mu, muu, muv, mudf, cqu, cqv,
+               msfux, msfuy, msfvx, msfvx_inv, msfvy, fnm, fnp, rdnw, rdx, rdy, dts, cf1, cf2, cf3, emdiv,
+               periodic_x, specified, nested,
+               ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,
+               its, ite, jts, jte, kts, kte, *, members=1, stream=None, dtype=None):
+    """advance_uv in front of an acoustic sub-step (``amt_advance_uv_device_f32/_f64``, header section 17) on a patch's
+    (``members`` > 1: a member-stacked ensemble's) torch device tensors or device addresses (then with ``dtype``): ``u`` and ``v``
+    are advanced in place by the horizontal pressure gradient of ``p``, ``al``, ``ph`` against the base state ``pb``, ``alt``,
+    ``php`` and by the divergence damping of ``mudf``.  ``fnm``, ``fnp``, ``rdnw`` are level arrays the members share.  The mass
+    cells at ``i_start-1`` and ``j_start-1`` are the caller's to fill.  Asynchronous on ``stream`` (default: torch's current)."""
+    L = _lib.load_library()
+    n3, n2, n1 = (jme - jms + 1) * (kme - kms + 1) * (ime - ims + 1), (jme - jms + 1) * (ime - ims + 1), kme - kms + 1
+    arrays = (u, v, ru_tend, rv_tend, p, pb, ph, php, alt, al, mu, muu, muv, mudf, cqu, cqv, msfux, msfuy, msfvx, msfvx_inv, msfvy,
+              fnm, fnp, rdnw)
+    _stage_call("advance_uv", L.amt_advance_uv_device_f32, L.amt_advance_uv_device_f64, arrays, set(),
+                [n3] * 10 + [n2] * 4 + [n3] * 2 + [n2] * 5 + [-n1] * 3, members, stream, dtype,
+                lambda q: [int(bool(non_hydrostatic))] + q + [float(x) for x in (rdx, rdy, dts, cf1, cf2, cf3, emdiv)]
+                + [int(bool(periodic_x)), int(bool(specified)), int(bool(nested))],
+                (ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte))
+
+
 def advance_mu_t(ww, ww_1, u, u_1, v, v_1, mu, mut, muave, muts, muu, muv, mudf, t, t_1,
                  t_ave, ft, mu_tend, rdx, rdy, dts, epssm, dnw, fnm, fnp, rdnw,
                  msfuy, msfvx_inv, msftx, msfty, config_flags,

@@ -20,6 +20,7 @@ void amt_handle_close(amt_domain *d)
     DeviceScope scope(d->device);
     amt_diag_release(d);
     amt_sumflux_release(d);
+    amt_uv_release(d);
     amt_p_rho_release(d);
     amt_stage_release(d);
     if (d->owns_fields)
@@ -342,8 +343,10 @@ int handle_step_t(const char *who, amt_domain *d, int members, bool stacked, int
     // an armed guard that already shows a finding: nothing is enqueued (no wait: the record is in host memory)
     if (d->guard_every) { const int rc = amt_diag_guard_status(who, d); if (rc) return rc; }
     for (int s = 0; s < n_sweeps; ++s) {
+        // the momentum update opens the sub-step, where WRF has its advance_uv call: u and v are final behind it
+        int rc = d->uv_per_sweep ? amt_uv_domain(who, d, members) : AMT_OK;
         // cyclic boundaries: the wrap cells are refreshed in front of every sweep, on the same stream (the inputs are final there)
-        int rc = d->cyclic ? amt_cyclic_refresh_domain(who, d, d->cyclic, members) : AMT_OK;
+        if (rc == AMT_OK && d->cyclic) rc = amt_cyclic_refresh_domain(who, d, d->cyclic, members);
         // every member in one launch; a domain takes the single-patch launch, an ensemble the stacked one also for one member
         if (rc == AMT_OK)
             rc = stacked ? amt_device_call_ensemble<T>(d->stream, d->variant, members, a)
@@ -360,15 +363,16 @@ int handle_step_t(const char *who, amt_domain *d, int members, bool stacked, int
 // accumulators stay as they are), nor a pressure diagnosis.  The settings of the sequence above that such sweeps must not see are saved and restored here.
 struct StepExtrasPause {
     amt_domain *d;
-    int every, spec_bdy, sumflux_n, p_rho_per_sweep;
+    int every, spec_bdy, sumflux_n, p_rho_per_sweep, uv_per_sweep;
     explicit StepExtrasPause(amt_domain *dom)
-        : d(dom), every(dom->guard_every), spec_bdy(dom->spec_bdy), sumflux_n(dom->sumflux_n), p_rho_per_sweep(dom->p_rho_per_sweep)
+        : d(dom), every(dom->guard_every), spec_bdy(dom->spec_bdy), sumflux_n(dom->sumflux_n), p_rho_per_sweep(dom->p_rho_per_sweep),
+          uv_per_sweep(dom->uv_per_sweep)
     {
-        d->guard_every = 0; d->spec_bdy = 0; d->sumflux_n = 0; d->p_rho_per_sweep = 0;
+        d->guard_every = 0; d->spec_bdy = 0; d->sumflux_n = 0; d->p_rho_per_sweep = 0; d->uv_per_sweep = 0;
     }
     ~StepExtrasPause()
     {
-        d->guard_every = every; d->spec_bdy = spec_bdy; d->sumflux_n = sumflux_n; d->p_rho_per_sweep = p_rho_per_sweep;
+        d->guard_every = every; d->spec_bdy = spec_bdy; d->sumflux_n = sumflux_n; d->p_rho_per_sweep = p_rho_per_sweep; d->uv_per_sweep = uv_per_sweep;
     }
 };
 }  // namespace
@@ -464,6 +468,17 @@ void *amt_handle_p_rho_ptr(amt_domain *d, int which) { return which < 0 || which
 
 int amt_handle_p_rho(const char *who, amt_domain *d, int members, int step) { return amt_p_rho_domain(who, d, members, step); }
 
+// The momentum update that opens an acoustic sub-step (header section 17): with per_sweep a line of the sweep sequence above.
+int amt_handle_set_uv(const char *who, amt_domain *d, int members, int on, int per_sweep, double emdiv, double cf1, double cf2, double cf3,
+                      void *const arr[9])
+{
+    return amt_uv_set_domain(who, d, members, on, per_sweep, emdiv, cf1, cf2, cf3, arr);
+}
+
+void *amt_handle_uv_ptr(amt_domain *d, int which) { return which < 0 || which > 8 ? nullptr : d->uv_arr[which]; }
+
+int amt_handle_uv(const char *who, amt_domain *d, int members) { return amt_uv_domain(who, d, members); }
+
 extern "C" int amt_domain_cyclic_fill(amt_domain *d, int axes)
 {
     return d ? amt_handle_cyclic_fill("amt_domain_cyclic_fill", d, 1, axes) : amt_null_domain();
@@ -503,6 +518,14 @@ extern "C" int amt_domain_set_p_rho(amt_domain *d, int mode, int per_sweep, doub
     return d ? amt_handle_set_p_rho("amt_domain_set_p_rho", d, 1, mode, per_sweep, t0, smdiv, al, p, ph, pm1, alt, c2a, znu, dnw)
              : amt_null_domain();
 }
+extern "C" int amt_domain_set_uv(amt_domain *d, int on, int per_sweep, double emdiv, double cf1, double cf2, double cf3, void *ru_tend,
+                                void *rv_tend, void *pb, void *php, void *cqu, void *cqv, void *msfux, void *msfvx, void *msfvy)
+{
+    void *const arr[9] = {ru_tend, rv_tend, pb, php, cqu, cqv, msfux, msfvx, msfvy};
+    return d ? amt_handle_set_uv("amt_domain_set_uv", d, 1, on, per_sweep, emdiv, cf1, cf2, cf3, arr) : amt_null_domain();
+}
+extern "C" void *amt_domain_uv_ptr(amt_domain *d, int which) { return d ? amt_handle_uv_ptr(d, which) : nullptr; }
+extern "C" int amt_domain_uv(amt_domain *d) { return d ? amt_handle_uv("amt_domain_uv", d, 1) : amt_null_domain(); }
 extern "C" void *amt_domain_p_rho_ptr(amt_domain *d, int which) { return d ? amt_handle_p_rho_ptr(d, which) : nullptr; }
 extern "C" int amt_domain_p_rho(amt_domain *d, int step)
 {

@@ -136,6 +136,14 @@ extern "C" int amt_ensemble_set_p_rho(amt_ensemble *e, int mode, int per_sweep, 
     return e ? amt_handle_set_p_rho("amt_ensemble_set_p_rho", &e->d, e->members, mode, per_sweep, t0, smdiv, al, p, ph, pm1, alt, c2a, znu, dnw)
              : amt_null_ensemble();
 }
+extern "C" int amt_ensemble_set_uv(amt_ensemble *e, int on, int per_sweep, double emdiv, double cf1, double cf2, double cf3, void *ru_tend,
+                                  void *rv_tend, void *pb, void *php, void *cqu, void *cqv, void *msfux, void *msfvx, void *msfvy)
+{
+    void *const arr[9] = {ru_tend, rv_tend, pb, php, cqu, cqv, msfux, msfvx, msfvy};
+    return e ? amt_handle_set_uv("amt_ensemble_set_uv", &e->d, e->members, on, per_sweep, emdiv, cf1, cf2, cf3, arr) : amt_null_ensemble();
+}
+extern "C" void *amt_ensemble_uv_ptr(amt_ensemble *e, int which) { return e ? amt_handle_uv_ptr(&e->d, which) : nullptr; }
+extern "C" int amt_ensemble_uv(amt_ensemble *e) { return e ? amt_handle_uv("amt_ensemble_uv", &e->d, e->members) : amt_null_ensemble(); }
 extern "C" void *amt_ensemble_p_rho_ptr(amt_ensemble *e, int which) { return e ? amt_handle_p_rho_ptr(&e->d, which) : nullptr; }
 extern "C" int amt_ensemble_p_rho(amt_ensemble *e, int step)
 {

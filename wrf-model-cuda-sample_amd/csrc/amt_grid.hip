@@ -515,10 +515,19 @@ int external_end_t(amt_grid *g)
     return rc ? rc : grid_bdy(g, "amt_grid_step_end");                    // behind the join: on the domain's stream
 }
 
+// advance_uv in front of every sweep needs the halo cells of p, al, ph, mu, mudf of the neighbours: that exchange is not
+// provided, so a stepper refuses to step a handle with the per-sweep setting on, before it enqueues anything
+int uv_refused(const amt_grid *g, const char *who)
+{
+    return g->dom->uv_per_sweep ? amt_fail(AMT_ERR_PRECONDITION, "%s: advance_uv in front of every sweep (amt_domain_set_uv, per_sweep) is not "
+                                           "provided under a stepper: the halo exchange of p, al, ph, mu, mudf is missing", who) : AMT_OK;
+}
+
 int external_begin(amt_grid *g)
 {
     int rc = external_only(g, "amt_grid_step_begin");
     if (rc) return rc;
+    if ((rc = uv_refused(g, "amt_grid_step_begin")) != AMT_OK) return rc;
     if (g->phase != 0) return amt_fail(AMT_ERR_INVALID_ARG, "amt_grid_step_begin: the previous sweep is still open (amt_grid_step_end closes it)");
     DeviceScope scope(g->dom->device);
     rc = g->dom->dtype_bytes == 8 ? external_begin_t<double>(g) : external_begin_t<float>(g);
@@ -543,6 +552,7 @@ int external_end(amt_grid *g)
 {
     int rc = external_only(g, "amt_grid_step_end");
     if (rc) return rc;
+    if ((rc = uv_refused(g, "amt_grid_step_end")) != AMT_OK) return rc;
     if (g->phase == 0) return amt_fail(AMT_ERR_INVALID_ARG, "amt_grid_step_end without amt_grid_step_begin");
     DeviceScope scope(g->dom->device);
     g->phase = 0;
@@ -657,6 +667,7 @@ int grid_exchange_only(amt_grid *g)
 int grid_step(amt_grid *g, int n_sweeps)
 {
     if (const int no = not_for_external(g, "amt_grid_step")) return no;
+    if (const int no = uv_refused(g, "amt_grid_step")) return no;
     DeviceScope scope(g->dom->device);
     return g->dom->dtype_bytes == 8 ? grid_step_t<double>(g, n_sweeps) : grid_step_t<float>(g, n_sweeps);
 }
@@ -664,6 +675,7 @@ int grid_step(amt_grid *g, int n_sweeps)
 int grid_step_timed(amt_grid *g, int n_sweeps, float *ms_total)
 {
     if (const int no = not_for_external(g, "amt_grid_step_timed")) return no;
+    if (const int no = uv_refused(g, "amt_grid_step_timed")) return no;
     DeviceScope scope(g->dom->device);
     AMT_HIP(hipEventRecord(g->t0, g->dom->stream));
     int rc = grid_step(g, n_sweeps);

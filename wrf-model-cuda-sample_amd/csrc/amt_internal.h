@@ -202,6 +202,11 @@ struct amt_domain {
     double p_rho_t0 = 0., p_rho_smdiv = 0.;
     void *p_rho_arr[8] = {};      // al, p, ph, pm1, alt, c2a (3-D, times the members of an ensemble), znu, dnw (1-D, shared)
     bool p_rho_owned = false;     // true: allocated by the library, freed with the setting or the handle
+    int uv_on = 0;                // the momentum update (amt_domain_set_uv); it reads the pressure diagnosis's al, p, ph, alt
+    int uv_per_sweep = 0;         // 1: one update precedes every sweep
+    double uv_emdiv = 0., uv_cf1 = 0., uv_cf2 = 0., uv_cf3 = 0.;
+    void *uv_arr[9] = {};         // ru_tend, rv_tend, pb, php, cqu, cqv (3-D, times the members), msfux, msfvx, msfvy (2-D)
+    bool uv_owned = false;        // true: allocated by the library, freed with the setting or the handle
     size_t count(int f) const
     {
         const size_t idim = ime - ims + 1, kdim = kme - kms + 1, jdim = jme - jms + 1;
@@ -287,6 +292,11 @@ int amt_handle_set_p_rho(const char *who, amt_domain *d, int members, int mode, 
                          void *al, void *p, void *ph, void *pm1, void *alt, void *c2a, void *znu, void *dnw);
 void *amt_handle_p_rho_ptr(amt_domain *d, int which);
 int amt_handle_p_rho(const char *who, amt_domain *d, int members, int step);
+// the momentum update that opens an acoustic sub-step (header section 17): in front of every sweep when per_sweep != 0
+int amt_handle_set_uv(const char *who, amt_domain *d, int members, int on, int per_sweep, double emdiv, double cf1, double cf2, double cf3,
+                      void *const arr[9]);
+void *amt_handle_uv_ptr(amt_domain *d, int which);
+int amt_handle_uv(const char *who, amt_domain *d, int members);
 int amt_handle_copy(amt_domain *d, void *dev, void *host, size_t bytes, bool up);
 int amt_handle_fill(amt_domain *d, int members, uint64_t field_mask, uint64_t seed,
                     long gi0, long gk0, long gj0, long gidim, long gkdim, long gjdim);
@@ -350,6 +360,12 @@ void amt_stage_release(amt_domain *d);
 //                         is off; the library's own arrays handed back: the mode and the scalars are set anew
 // ---------------------------------------------------------------------------
 #pragma GCC visibility push(hidden)
+// advance_uv (amt_uv.hip, header section 17) of `members` member-stacked patches on the domain's stream, behind the wrap refresh
+// of its eight read arrays on a cyclic handle; AMT_ERR_PRECONDITION while its setting or the pressure diagnosis's is off
+int amt_uv_domain(const char *who, amt_domain *d, int members);
+int amt_uv_set_domain(const char *who, amt_domain *d, int members, int on, int per_sweep, double emdiv, double cf1, double cf2, double cf3,
+                      void *const arr[9]);
+void amt_uv_release(amt_domain *d);
 int amt_p_rho_domain(const char *who, amt_domain *d, int members, int step);
 int amt_p_rho_set_domain(const char *who, amt_domain *d, int members, int mode, int per_sweep, double t0, double smdiv, void *const arr[8]);
 void amt_p_rho_release(amt_domain *d);

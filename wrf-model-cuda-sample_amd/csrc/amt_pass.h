@@ -52,7 +52,7 @@ inline int amt_pass_run(int rc, bool empty, const amt_domain &d, bool pointer_le
 // ---- the arrays a setting keeps in its handle: the caller's or, when the caller gives none, the library's -------------------
 struct AmtPassSetting {
     void **slot; bool *owned; int count;   // the `count` pointers in the amt_domain; owned: allocated by the library
-    size_t bytes[8];                       // of array k, when the library allocates
+    size_t bytes[9];                       // of array k, when the library allocates
     // "give all <three accumulators> or none", "<an accumulator> the library allocated, mixed with others", "the handle's
     // tile does not admit <the flux averages>", "no room for <three arrays> of %zu bytes"
     const char *all_of_them, *one_of_them, *pass, *room;

@@ -78,7 +78,7 @@ int amt_pass_setting_offer(const char *who, const AmtPassSetting &s, void *const
 int amt_pass_setting_take(const char *who, const amt_domain *d, int members, const AmtPassSetting &s, void *const *arr, int given,
                           bool same, const std::function<int(void *const *)> &check)
 {
-    void *mine[8] = {};
+    void *mine[9] = {};
     if (given) {
         if (*s.owned && !same)
             for (int k = 0; k < s.count; ++k)

@@ -9,7 +9,7 @@
 ! domain handle (device arrays kept across calls -- the kernel-only time the
 ! reference reports) and checks that both paths agree bit for bit.
 !
-!   advance_mu_t_driver [NI NK NJ [nsweeps [outdir [flags [placements [members [nsmall [bracket [pressure]]]]]]]]]
+!   advance_mu_t_driver [NI NK NJ [nsweeps [outdir [flags [placements [members [nsmall [bracket [pressure [momentum]]]]]]]]]]
 !     flags: 0 none, 1 specified, 2 nested, 3 specified+periodic_x
 !     placements: > 1 samples that many allocations of the resident state and keeps the fastest (amt_domain_tune_placement)
 !     members: > 0 adds an ensemble of that many members of the same shape (amt_ensemble_fill_synthetic, seeds seed + m),
@@ -20,6 +20,9 @@
 !              between small_step_prep and small_step_finish on the device (header section 15); 0 (the default): nothing more
 !     pressure: 1 with nsmall > 0 adds a Runge-Kutta stage whose sub-steps are each closed by calc_p_rho on the device (header
 !              section 16): hydrostatic on a domain handle, non-hydrostatic on an ensemble; 0 (the default): nothing more
+!     momentum: 1 adds advance_uv on the device (header section 17): through the pointer-level call, hydrostatic and, with at
+!              least three levels, non-hydrostatic, on the arrays of two resident handles, then as a handle setting on a domain
+!              (in front of a sweep) and on an ensemble; 0 (the default): nothing more
 !   With outdir the 7 updated arrays are written there as raw native-endian
 !   streams <name>.bin for an external checker; with members the moments as ens_<field>_<mean|var|lo|hi>.bin:
 !   ww over the whole memory, mu over the compute window, t over the memory less one cell on every side (zero outside).
@@ -48,7 +51,7 @@ program advance_mu_t_driver
   real(c_float) :: ms
   integer(kind=8) :: c0, c1, cmid, hz
   real(kind=8) :: cells, secs
-  integer :: nbad, ndef, ntune, members, nsmall, bracket, pressure
+  integer :: nbad, ndef, ntune, members, nsmall, bracket, pressure, momentum
   integer(c_int) :: nslots, slot_ids(16)
   real(c_float) :: tune_ms(8)
 
@@ -85,6 +88,10 @@ program advance_mu_t_driver
   pressure = 0
   if (command_argument_count() >= 11) then
      call get_command_argument(11, arg); read (arg, *) pressure
+  end if
+  momentum = 0
+  if (command_argument_count() >= 12) then
+     call get_command_argument(12, arg); read (arg, *) momentum
   end if
   config_flags%specified  = (iflag == 1 .or. iflag == 3)
   config_flags%nested     = (iflag == 2)
@@ -292,6 +299,7 @@ program advance_mu_t_driver
   if (nsmall > 0) call flux_averages()
   if (nsmall > 0 .and. bracket == 1) call stage_bracket()
   if (nsmall > 0 .and. pressure == 1) call pressure_diagnosis()
+  if (momentum == 1) call momentum_update()
 
 contains
 
@@ -409,6 +417,163 @@ contains
                                  ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte)
     end if
     call amt_check(rc, 'amt_p_rho_device')
+  end subroutine
+
+  ! One advance_uv through the pointer-level call on the stream of a resident handle `d`, whose u and v it advances: the other
+  ! arrays are fields of `d` and of a second handle `px` (p, pb, ph, php, alt, al are its ww, ww_1, u, u_1, v, v_1), filled by the
+  ! generator.  Hydrostatic, then non-hydrostatic where the column has three levels of p; u must have moved and stay finite.
+  subroutine momentum_update()
+    type(c_ptr) :: d, px
+    real(wp), allocatable, target :: a3(:,:,:), b3(:,:,:)
+    integer(c_int) :: nh
+    integer :: moved
+    allocate (a3(ims:ime,kms:kme,jms:jme), b3(ims:ime,kms:kme,jms:jme))
+    call make_domain(d, seed)
+    call make_domain(px, seed + 3_c_int64_t)
+    do nh = 0, merge(1, 0, kde >= 4)
+       call amt_check(amt_domain_download(d, AMT_F_U, c_loc(a3)), 'amt_domain_download')
+       call uv_device(d, px, nh)
+       call amt_check(amt_domain_sync(d), 'amt_domain_sync')
+       call amt_check(amt_domain_download(d, AMT_F_U, c_loc(b3)), 'amt_domain_download')
+       moved = count(a3 /= b3)
+       if (moved == 0 .or. any(b3 /= b3)) error stop 11
+       print '(a,i0,a,i0,a,es24.16)', 'advance_uv on the device, non_hydrostatic = ', nh, ': ', moved, ' elements of u moved, sum = ', &
+             sum(real(b3, kind=8))
+    end do
+    call amt_check(amt_domain_destroy(d), 'amt_domain_destroy')
+    call amt_check(amt_domain_destroy(px), 'amt_domain_destroy')
+    call uv_on_handles()
+  end subroutine
+
+  ! The same update as a handle setting: hydrostatic on a domain handle, in front of a sweep (per_sweep) and once by the call;
+  ! non-hydrostatic (where the column has three levels of p) on an ensemble.  The stage bracket's arrays are fields of `ex`, the
+  ! pressure diagnosis's of `px` as in pressure_diagnosis, the update's nine -- ru_tend, rv_tend, pb, php, cqu, cqv, msfux, msfvx,
+  ! msfvy -- fields of `qx`.
+  subroutine uv_on_handles()
+    type(c_ptr) :: d, ex, px, qx, own, e, eex, epx, eqx
+    real(wp), allocatable, target :: a3(:,:,:), b3(:,:,:)
+    integer(c_int) :: mm, k, mode
+    integer(c_int), parameter :: xf(4) = [AMT_F_T, AMT_F_MU, AMT_F_MUAVE, AMT_F_MUT]
+    integer(c_int), parameter :: pf(8) = [AMT_F_WW, AMT_F_WW_1, AMT_F_U, AMT_F_U_1, AMT_F_V, AMT_F_V_1, AMT_F_FNM, AMT_F_DNW]
+    integer(c_int), parameter :: qf(9) = [AMT_F_FT, AMT_F_T_AVE, AMT_F_WW_1, AMT_F_U_1, AMT_F_T, AMT_F_T_1, AMT_F_MSFTX, AMT_F_MSFTY, &
+                                          AMT_F_MSFUY]
+    real(c_double), parameter :: t0 = 300.0_c_double, smdiv = 0.1_c_double, emdiv = 0.01_c_double
+    real(c_double), parameter :: cf1 = 1.5_c_double, cf2 = -0.75_c_double, cf3 = 0.25_c_double
+    mm = int(max(members, 1), c_int)
+    allocate (a3(ims:ime,kms:kme,jms:jme), b3(ims:ime,kms:kme,jms:jme))
+    call make_domain(d, seed)
+    call make_domain(ex, seed + 1_c_int64_t)
+    call make_domain(px, seed + 2_c_int64_t)
+    call make_domain(qx, seed + 3_c_int64_t)
+    call make_domain(own, seed)
+    ! off until set; the setting needs the pressure diagnosis; a mix of given and missing arrays is refused
+    if (c_associated(amt_domain_uv_ptr(d, 0_c_int))) error stop 12
+    if (amt_domain_uv(d) /= AMT_ERR_PRECONDITION) error stop 12
+    if (amt_domain_set_uv(d, 1_c_int, 1_c_int, emdiv, cf1, cf2, cf3, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, &
+                          c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr) /= AMT_ERR_PRECONDITION) error stop 12
+    call amt_check(amt_domain_set_stage(d, 1_c_int, amt_domain_field_ptr(ex, xf(1)), amt_domain_field_ptr(ex, xf(2)),        &
+                   amt_domain_field_ptr(ex, xf(3)), amt_domain_field_ptr(ex, xf(4))), 'amt_domain_set_stage')
+    call amt_check(amt_domain_set_p_rho(d, 2_c_int, 0_c_int, t0, smdiv, amt_domain_field_ptr(px, pf(1)),                     &
+                   amt_domain_field_ptr(px, pf(2)), amt_domain_field_ptr(px, pf(3)), amt_domain_field_ptr(px, pf(4)),        &
+                   amt_domain_field_ptr(px, pf(5)), amt_domain_field_ptr(px, pf(6)), amt_domain_field_ptr(px, pf(7)),        &
+                   amt_domain_field_ptr(px, pf(8))), 'amt_domain_set_p_rho')
+    if (amt_domain_set_uv(d, 1_c_int, 1_c_int, emdiv, cf1, cf2, cf3, amt_domain_field_ptr(qx, qf(1)), c_null_ptr, c_null_ptr,   &
+                          c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr) /= AMT_ERR_INVALID_ARG) error stop 12
+    call amt_check(amt_domain_set_uv(d, 1_c_int, 1_c_int, emdiv, cf1, cf2, cf3, amt_domain_field_ptr(qx, qf(1)),              &
+                   amt_domain_field_ptr(qx, qf(2)), amt_domain_field_ptr(qx, qf(3)), amt_domain_field_ptr(qx, qf(4)),        &
+                   amt_domain_field_ptr(qx, qf(5)), amt_domain_field_ptr(qx, qf(6)), amt_domain_field_ptr(qx, qf(7)),        &
+                   amt_domain_field_ptr(qx, qf(8)), amt_domain_field_ptr(qx, qf(9))), 'amt_domain_set_uv')
+    if (.not. c_associated(amt_domain_uv_ptr(d, 8_c_int), amt_domain_field_ptr(qx, qf(9)))) error stop 12
+    ! the library's own nine arrays on another handle: allocated, named, freed
+    call amt_check(amt_domain_set_stage(own, 1_c_int, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr), 'amt_domain_set_stage')
+    call amt_check(amt_domain_set_p_rho(own, 2_c_int, 0_c_int, t0, smdiv, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr,   &
+                   c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr), 'amt_domain_set_p_rho')
+    call amt_check(amt_domain_set_uv(own, 1_c_int, 0_c_int, emdiv, cf1, cf2, cf3, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, &
+                   c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr), 'amt_domain_set_uv')
+    do k = 0, 8
+       if (.not. c_associated(amt_domain_uv_ptr(own, k))) error stop 12
+    end do
+    call amt_check(amt_domain_set_uv(own, 0_c_int, 0_c_int, emdiv, cf1, cf2, cf3, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, &
+                   c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr), 'amt_domain_set_uv')
+    if (c_associated(amt_domain_uv_ptr(own, 0_c_int))) error stop 12
+    call amt_check(amt_domain_destroy(own), 'amt_domain_destroy')
+    ! prep, the step-0 diagnosis, one update by the call, then one more in front of the sweep
+    call amt_check(amt_domain_stage_prep(d, 1_c_int), 'amt_domain_stage_prep')
+    call amt_check(amt_domain_p_rho(d, 0_c_int), 'amt_domain_p_rho')
+    call amt_check(amt_domain_download(d, AMT_F_U, c_loc(a3)), 'amt_domain_download')
+    call amt_check(amt_domain_uv(d), 'amt_domain_uv')
+    call amt_check(amt_domain_download(d, AMT_F_U, c_loc(b3)), 'amt_domain_download')
+    if (count(a3 /= b3) == 0) error stop 12
+    call amt_check(amt_domain_step(d, 1_c_int), 'amt_domain_step')
+    call amt_check(amt_domain_download(d, AMT_F_U, c_loc(a3)), 'amt_domain_download')
+    if (count(a3 /= b3) == 0) error stop 12
+    ! an ensemble: every member's update in one launch
+    mode = merge(1_c_int, 2_c_int, kde >= 4)
+    call make_ensemble(e, mm, seed)
+    call make_ensemble(eex, mm, seed + 1_c_int64_t)
+    call make_ensemble(epx, mm, seed + 2_c_int64_t)
+    call make_ensemble(eqx, mm, seed + 3_c_int64_t)
+    call amt_check(amt_ensemble_set_stage(e, 1_c_int, amt_ensemble_field_ptr(eex, xf(1)), amt_ensemble_field_ptr(eex, xf(2)),  &
+                   amt_ensemble_field_ptr(eex, xf(3)), amt_ensemble_field_ptr(eex, xf(4))), 'amt_ensemble_set_stage')
+    call amt_check(amt_ensemble_set_p_rho(e, mode, 0_c_int, t0, smdiv, amt_ensemble_field_ptr(epx, pf(1)),                  &
+                   amt_ensemble_field_ptr(epx, pf(2)), amt_ensemble_field_ptr(epx, pf(3)), amt_ensemble_field_ptr(epx, pf(4)), &
+                   amt_ensemble_field_ptr(epx, pf(5)), amt_ensemble_field_ptr(epx, pf(6)), amt_ensemble_field_ptr(epx, pf(7)), &
+                   amt_ensemble_field_ptr(epx, pf(8))), 'amt_ensemble_set_p_rho')
+    call amt_check(amt_ensemble_set_uv(e, 1_c_int, 0_c_int, emdiv, cf1, cf2, cf3, amt_ensemble_field_ptr(eqx, qf(1)),         &
+                   amt_ensemble_field_ptr(eqx, qf(2)), amt_ensemble_field_ptr(eqx, qf(3)), amt_ensemble_field_ptr(eqx, qf(4)), &
+                   amt_ensemble_field_ptr(eqx, qf(5)), amt_ensemble_field_ptr(eqx, qf(6)), amt_ensemble_field_ptr(eqx, qf(7)), &
+                   amt_ensemble_field_ptr(eqx, qf(8)), amt_ensemble_field_ptr(eqx, qf(9))), 'amt_ensemble_set_uv')
+    if (.not. c_associated(amt_ensemble_uv_ptr(e, 2_c_int), amt_ensemble_field_ptr(eqx, qf(3)))) error stop 12
+    call amt_check(amt_ensemble_stage_prep(e, 1_c_int), 'amt_ensemble_stage_prep')
+    call amt_check(amt_ensemble_p_rho(e, 0_c_int), 'amt_ensemble_p_rho')
+    call amt_check(amt_ensemble_uv(e), 'amt_ensemble_uv')
+    call amt_check(amt_ensemble_sync(e), 'amt_ensemble_sync')
+    print '(a,i0,a,es24.16)', 'advance_uv as a handle setting, on a domain in front of a sweep and on an ensemble of ', mm,      &
+       ' members; checksum of u: ', sum(real(a3(its:ite, kts:kte-1, jts:jte-1), 8))
+    call amt_check(amt_ensemble_destroy(e), 'amt_ensemble_destroy')
+    call amt_check(amt_ensemble_destroy(eex), 'amt_ensemble_destroy')
+    call amt_check(amt_ensemble_destroy(epx), 'amt_ensemble_destroy')
+    call amt_check(amt_ensemble_destroy(eqx), 'amt_ensemble_destroy')
+    call amt_check(amt_domain_destroy(d), 'amt_domain_destroy')
+    call amt_check(amt_domain_destroy(ex), 'amt_domain_destroy')
+    call amt_check(amt_domain_destroy(px), 'amt_domain_destroy')
+    call amt_check(amt_domain_destroy(qx), 'amt_domain_destroy')
+  end subroutine
+
+  subroutine uv_device(h, px, nh)
+    type(c_ptr), intent(in) :: h, px
+    integer(c_int), intent(in) :: nh
+    type(c_ptr) :: stream
+    integer(c_int) :: fl(3)
+    stream = amt_domain_stream(h)
+    fl = [merge(1_c_int, 0_c_int, config_flags%periodic_x), merge(1_c_int, 0_c_int, config_flags%specified),               &
+          merge(1_c_int, 0_c_int, config_flags%nested)]
+    if (storage_size(rdx) == 64) then
+       rc = amt_advance_uv_device_f64(stream, 1_c_int, nh, amt_domain_field_ptr(h, AMT_F_U), amt_domain_field_ptr(h, AMT_F_V),       &
+               amt_domain_field_ptr(h, AMT_F_FT), amt_domain_field_ptr(h, AMT_F_FT), amt_domain_field_ptr(px, AMT_F_WW),          &
+               amt_domain_field_ptr(px, AMT_F_WW_1), amt_domain_field_ptr(px, AMT_F_U), amt_domain_field_ptr(px, AMT_F_U_1),      &
+               amt_domain_field_ptr(px, AMT_F_V), amt_domain_field_ptr(px, AMT_F_V_1), amt_domain_field_ptr(h, AMT_F_MU),         &
+               amt_domain_field_ptr(h, AMT_F_MUU), amt_domain_field_ptr(h, AMT_F_MUV), amt_domain_field_ptr(h, AMT_F_MU_TEND),    &
+               amt_domain_field_ptr(h, AMT_F_T), amt_domain_field_ptr(h, AMT_F_T_1), amt_domain_field_ptr(h, AMT_F_MSFTX),        &
+               amt_domain_field_ptr(h, AMT_F_MSFUY), amt_domain_field_ptr(h, AMT_F_MSFTY),                                        &
+               amt_domain_field_ptr(h, AMT_F_MSFVX_INV), amt_domain_field_ptr(h, AMT_F_MSFTY), amt_domain_field_ptr(h, AMT_F_FNM), &
+               amt_domain_field_ptr(h, AMT_F_FNP), amt_domain_field_ptr(h, AMT_F_RDNW), real(rdx, c_double), real(rdy, c_double), &
+               real(dts, c_double), 1.5_c_double, -0.75_c_double, 0.25_c_double, 0.01_c_double, fl(1), fl(2), fl(3),              &
+               ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte)
+    else
+       rc = amt_advance_uv_device_f32(stream, 1_c_int, nh, amt_domain_field_ptr(h, AMT_F_U), amt_domain_field_ptr(h, AMT_F_V),       &
+               amt_domain_field_ptr(h, AMT_F_FT), amt_domain_field_ptr(h, AMT_F_FT), amt_domain_field_ptr(px, AMT_F_WW),          &
+               amt_domain_field_ptr(px, AMT_F_WW_1), amt_domain_field_ptr(px, AMT_F_U), amt_domain_field_ptr(px, AMT_F_U_1),      &
+               amt_domain_field_ptr(px, AMT_F_V), amt_domain_field_ptr(px, AMT_F_V_1), amt_domain_field_ptr(h, AMT_F_MU),         &
+               amt_domain_field_ptr(h, AMT_F_MUU), amt_domain_field_ptr(h, AMT_F_MUV), amt_domain_field_ptr(h, AMT_F_MU_TEND),    &
+               amt_domain_field_ptr(h, AMT_F_T), amt_domain_field_ptr(h, AMT_F_T_1), amt_domain_field_ptr(h, AMT_F_MSFTX),        &
+               amt_domain_field_ptr(h, AMT_F_MSFUY), amt_domain_field_ptr(h, AMT_F_MSFTY),                                        &
+               amt_domain_field_ptr(h, AMT_F_MSFVX_INV), amt_domain_field_ptr(h, AMT_F_MSFTY), amt_domain_field_ptr(h, AMT_F_FNM), &
+               amt_domain_field_ptr(h, AMT_F_FNP), amt_domain_field_ptr(h, AMT_F_RDNW), real(rdx, c_float), real(rdy, c_float),   &
+               real(dts, c_float), 1.5_c_float, -0.75_c_float, 0.25_c_float, 0.01_c_float, fl(1), fl(2), fl(3),                   &
+               ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme, its, ite, jts, jte, kts, kte)
+    end if
+    call amt_check(rc, 'amt_advance_uv_device')
   end subroutine
 
   ! Two Runge-Kutta stages (rk_step 1 without, rk_step 2 with a diabatic heating) whose acoustic loops of nsmall sub-steps run

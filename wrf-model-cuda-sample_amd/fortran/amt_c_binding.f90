@@ -1237,6 +1237,84 @@ MODULE amt_c_binding
          integer(c_int), value :: its, ite, jts, jte, kts, kte
          integer(c_int) :: rc
       end function
+      ! (17) the momentum update that opens an acoustic sub-step: advance_uv.  Pointer level (members = 1 for a single patch):
+      ! every array is a DEVICE pointer; asynchronous on hip_stream.  u and v are advanced in place; the mass cells at i_start-1
+      ! and j_start-1 are the caller's to fill; non_hydrostatic /= 0 adds the vertical pressure term (kde >= 4)
+      function amt_advance_uv_device_f32(hip_stream, members, non_hydrostatic, u, v, ru_tend, rv_tend, p, pb, ph, php, alt, al,   &
+                                         mu, muu, muv, mudf, cqu, cqv, msfux, msfuy, msfvx, msfvx_inv, msfvy, fnm, fnp, rdnw, &
+                                         rdx, rdy, dts, cf1, cf2, cf3, emdiv, periodic_x, specified, nested,                 &
+                                         ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,                              &
+                                         its, ite, jts, jte, kts, kte) bind(C, name="amt_advance_uv_device_f32") result(rc)
+         import :: c_ptr, c_int, c_float
+         type(c_ptr), value :: hip_stream
+         integer(c_int), value :: members, non_hydrostatic
+         type(c_ptr), value :: u, v, ru_tend, rv_tend, p, pb, ph, php, alt, al, mu, muu, muv, mudf, cqu, cqv   ! device pointers
+         type(c_ptr), value :: msfux, msfuy, msfvx, msfvx_inv, msfvy, fnm, fnp, rdnw                           ! device pointers
+         real(c_float), value :: rdx, rdy, dts, cf1, cf2, cf3, emdiv
+         integer(c_int), value :: periodic_x, specified, nested
+         integer(c_int), value :: ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme
+         integer(c_int), value :: its, ite, jts, jte, kts, kte
+         integer(c_int) :: rc
+      end function
+      function amt_advance_uv_device_f64(hip_stream, members, non_hydrostatic, u, v, ru_tend, rv_tend, p, pb, ph, php, alt, al,   &
+                                         mu, muu, muv, mudf, cqu, cqv, msfux, msfuy, msfvx, msfvx_inv, msfvy, fnm, fnp, rdnw, &
+                                         rdx, rdy, dts, cf1, cf2, cf3, emdiv, periodic_x, specified, nested,                 &
+                                         ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme,                              &
+                                         its, ite, jts, jte, kts, kte) bind(C, name="amt_advance_uv_device_f64") result(rc)
+         import :: c_ptr, c_int, c_double
+         type(c_ptr), value :: hip_stream
+         integer(c_int), value :: members, non_hydrostatic
+         type(c_ptr), value :: u, v, ru_tend, rv_tend, p, pb, ph, php, alt, al, mu, muu, muv, mudf, cqu, cqv   ! device pointers
+         type(c_ptr), value :: msfux, msfuy, msfvx, msfvx_inv, msfvy, fnm, fnp, rdnw                           ! device pointers
+         real(c_double), value :: rdx, rdy, dts, cf1, cf2, cf3, emdiv
+         integer(c_int), value :: periodic_x, specified, nested
+         integer(c_int), value :: ids, ide, jds, jde, kde, ims, ime, jms, jme, kms, kme
+         integer(c_int), value :: its, ite, jts, jte, kts, kte
+         integer(c_int) :: rc
+      end function
+      ! (17) on a handle: on = 0 off (the default); on /= 0 with nine c_null_ptr: the library allocates ru_tend, rv_tend, pb, php,
+      ! cqu, cqv, msfux, msfvx, msfvy (filled through amt_domain_uv_ptr), with nine device pointers: the caller's.  It needs
+      ! amt_domain_set_p_rho.  per_sweep /= 0: one update precedes every sweep of amt_domain_step; amt_domain_uv runs one now
+      function amt_domain_set_uv(handle, on, per_sweep, emdiv, cf1, cf2, cf3, ru_tend, rv_tend, pb, php, cqu, cqv, msfux, msfvx,    &
+                                 msfvy) bind(C, name="amt_domain_set_uv") result(rc)
+         import :: c_ptr, c_int, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: on, per_sweep
+         real(c_double), value :: emdiv, cf1, cf2, cf3
+         type(c_ptr), value :: ru_tend, rv_tend, pb, php, cqu, cqv, msfux, msfvx, msfvy      ! device pointers, all or none
+         integer(c_int) :: rc
+      end function
+      function amt_domain_uv_ptr(handle, which) bind(C, name="amt_domain_uv_ptr") result(ptr)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: which
+         type(c_ptr) :: ptr
+      end function
+      function amt_domain_uv(handle) bind(C, name="amt_domain_uv") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_set_uv(handle, on, per_sweep, emdiv, cf1, cf2, cf3, ru_tend, rv_tend, pb, php, cqu, cqv, msfux, msfvx,    &
+                                 msfvy) bind(C, name="amt_ensemble_set_uv") result(rc)
+         import :: c_ptr, c_int, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: on, per_sweep
+         real(c_double), value :: emdiv, cf1, cf2, cf3
+         type(c_ptr), value :: ru_tend, rv_tend, pb, php, cqu, cqv, msfux, msfvx, msfvy      ! device pointers, all or none
+         integer(c_int) :: rc
+      end function
+      function amt_ensemble_uv_ptr(handle, which) bind(C, name="amt_ensemble_uv_ptr") result(ptr)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int), value :: which
+         type(c_ptr) :: ptr
+      end function
+      function amt_ensemble_uv(handle) bind(C, name="amt_ensemble_uv") result(rc)
+         import :: c_ptr, c_int
+         type(c_ptr), value :: handle
+         integer(c_int) :: rc
+      end function
       ! set: mode = 0 off (the default); mode = 1 or 2 with eight c_null_ptr: the library allocates al, p, ph, pm1, alt, c2a, znu,
       ! dnw (the host fills alt, c2a, ph, znu, dnw through amt_domain_p_rho_ptr), with eight device pointers: the caller's.  It
       ! needs amt_domain_set_stage.  per_sweep /= 0: one diagnosis follows every sweep of amt_domain_step, amt_slab_step,

@@ -232,6 +232,14 @@ SYMBOLS = {
     "amt_ensemble_set_p_rho": (_I, [_P, _I, _I, ctypes.c_double, ctypes.c_double] + [_P] * 8),
     "amt_ensemble_p_rho_ptr": (_P, [_P, _I]),
     "amt_ensemble_p_rho": (_I, [_P, _I]),
+    "amt_advance_uv_device_f32": (_I, [_P, _I, _I] + [_P] * 24 + [ctypes.c_float] * 7 + [_I] * 20),
+    "amt_advance_uv_device_f64": (_I, [_P, _I, _I] + [_P] * 24 + [ctypes.c_double] * 7 + [_I] * 20),
+    "amt_domain_set_uv": (_I, [_P, _I, _I] + [ctypes.c_double] * 4 + [_P] * 9),
+    "amt_domain_uv_ptr": (_P, [_P, _I]),
+    "amt_domain_uv": (_I, [_P]),
+    "amt_ensemble_set_uv": (_I, [_P, _I, _I] + [ctypes.c_double] * 4 + [_P] * 9),
+    "amt_ensemble_uv_ptr": (_P, [_P, _I]),
+    "amt_ensemble_uv": (_I, [_P]),
     "amt_halo_plan": (_I, [_I] * (4 + 17 + 5) + [ctypes.POINTER(HaloMessage), _I, ctypes.POINTER(_I)]),
     "amt_grid_halo_messages": (_I, [_P, ctypes.POINTER(HaloMessage), _I, ctypes.POINTER(_I)]),
     "amt_slab_halo_messages": (_I, [_P, ctypes.POINTER(HaloMessage), _I, ctypes.POINTER(_I)]),
@@ -463,6 +471,27 @@ class ResidentHandle:
         """``p_rho``: one diagnosis now, asynchronous on the handle's stream (every member of an ensemble in one launch);
         ``step`` 0 is the call behind ``stage_prep``."""
         check(self._fn("p_rho")(self.handle, int(step)))
+
+    # the momentum update that opens an acoustic sub-step: advance_uv (header section 17)
+    def set_uv(self, on: bool, per_sweep: bool = False, emdiv: float = 0.0, cf1: float = 0.0, cf2: float = 0.0, cf3: float = 0.0,
+               ru_tend=None, rv_tend=None, pb=None, php=None, cqu=None, cqv=None, msfux=None, msfvx=None, msfvy=None) -> None:
+        """``set_uv``: without arrays the library allocates ``ru_tend``, ``rv_tend``, ``pb``, ``php``, ``cqu``, ``cqv`` (one 3-D
+        field's extents times the members) and ``msfux``, ``msfvx``, ``msfvy`` (one 2-D field's), which the host fills
+        (``uv_ptr``); otherwise all nine are device tensors (or addresses) which the caller keeps alive.  Needs ``set_p_rho``,
+        whose ``al``, ``p``, ``ph``, ``alt`` it reads; mode 1 there is the non-hydrostatic form here.  ``per_sweep``: every sweep
+        of ``step`` is preceded by one update."""
+        check(self._fn("set_uv")(self.handle, int(bool(on)), int(bool(per_sweep)), float(emdiv), float(cf1), float(cf2), float(cf3),
+                                 *[_address(a) for a in (ru_tend, rv_tend, pb, php, cqu, cqv, msfux, msfvx, msfvy)]))
+
+    def uv_ptr(self, which: int) -> int:
+        """Device address of ru_tend (0), rv_tend (1), pb (2), php (3), cqu (4), cqv (5), msfux (6), msfvx (7) or msfvy (8); 0
+        while the setting is off."""
+        return int(self._fn("uv_ptr")(self.handle, int(which)) or 0)
+
+    def uv(self) -> None:
+        """``uv``: one update now, asynchronous on the handle's stream (every member of an ensemble in one launch), behind the
+        wrap refresh of its read arrays on a cyclic handle."""
+        check(self._fn("uv")(self.handle))
 
 
 def _address(a):

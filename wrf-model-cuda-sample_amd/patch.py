@@ -547,6 +547,20 @@ class _NativeStepper:
         with self._dev():
             self._lib.check(self.L.amt_domain_p_rho(self._dom, int(step)))
 
+    def set_uv(self, on: bool = True, per_sweep: bool = False, emdiv: float = 0.0, cf1: float = 0.0, cf2: float = 0.0, cf3: float = 0.0):
+        """The library allocates ru_tend, rv_tend, pb, php, cqu, cqv, msfux, msfvx, msfvy (``uv_ptr``); off frees them.  With
+        ``per_sweep`` the stepper's step calls are refused: the halo exchange of p, al, ph, mu, mudf is not provided."""
+        with self._dev():
+            self._lib.check(self.L.amt_domain_set_uv(self._dom, int(bool(on)), int(bool(per_sweep)), float(emdiv), float(cf1), float(cf2),
+                                                     float(cf3), *[None] * 9))
+
+    def uv_ptr(self, which: int) -> int:
+        return int(self.L.amt_domain_uv_ptr(self._dom, int(which)) or 0)
+
+    def uv(self):
+        with self._dev():
+            self._lib.check(self.L.amt_domain_uv(self._dom))
+
     def close(self):
         if self._h:
             with self._dev():
